@@ -16,6 +16,18 @@ The other BASELINE.json configs are presets (``--config``):
                   /root/reference/pytorch/resnet/main.py:36-54,164)
 
 Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--graph 1] [--breakdown N]
+                        [--full] [--dump-outputs DIR]
+
+A plain run does what the headline figure needs and nothing more: set up, warm up, time ``--steps``
+training steps, print the result line.  ``--full`` adds the instruments that ride along or take
+untimed steps of their own: the in-kernel shader-clock stamps around the timed steps (``sclk_mhz``,
+``clock``), at N > 1 (or ``--rehearse``) the HIP-event phase breakdown (``dist.comm_exposed_ms``) and,
+with an RCCL reducer, the per-bucket all-reduce probe (``dist.bucket_probe``).  Without it those
+fields are null.  ``--dump-outputs DIR`` writes what the last timed step left, as float32
+``DIR/<name>.npy`` on rank 0: ``loss``, ``logits`` (the model's output), ``params`` and ``grads``
+(the flat master weights after the update and the flat gradients it consumed); an array of more
+than 2 Mi elements is stored as a fixed seeded sample of that many.  Inputs, labels and initial weights are seeded, so two builds given the same
+arguments are compared output for output.
 
 Launch: one rank per GPU.  Under torch.distributed.run / torchrun or mpirun the ranks come from the
 launcher's environment and ``--gpus`` must equal the world size (checked; a mismatch exits 2).
@@ -90,6 +102,25 @@ def launch_ranks(n: int, launcher: str, argv, script: str | None = None) -> int:
     return subprocess.call(cmd, env=env)
 
 
+DUMP_MAX = 2 << 20   # elements per dumped array (float32: 8 MiB each, four arrays)
+
+
+def dump_outputs(path: str, tensors: dict) -> None:
+    """Write each tensor as float32 ``path/<name>.npy``; one of more than DUMP_MAX elements as a fixed
+    seeded sample (generator seed 0, sorted flat indices) of DUMP_MAX of them."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in tensors.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(t.numel(), (DUMP_MAX,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -145,8 +176,14 @@ def main():
                     help="compute precision of the native engine: bf16 (default, the BASELINE dtype) or fp32 "
                          "(the same kernels on fp32 storage -- how the reference trains ResNet-18 on CIFAR)")
     ap.add_argument("--bucket_probe", type=int, default=1,
-                    help="1 (default): with an RCCL reducer (N > 1 or --rccl1) and no hipGraph, one untimed step "
+                    help="1 (default; needs --full): with an RCCL reducer (N > 1 or --rccl1) and no hipGraph, one untimed step "
                          "after the timed region times every bucket all-reduce on the comm stream (dist.buckets)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the instruments a plain run leaves out: shader-clock stamps around the timed "
+                         "steps, the automatic phase breakdown at N > 1 / --rehearse, the bucket all-reduce probe")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's loss, logits, updated weights and gradients "
+                         "as float32 DIR/<name>.npy (rank 0; large arrays as a fixed seeded sample)")
     args = ap.parse_args()
     if args.rccl_channels is not None:
         os.environ["DLMPI_RCCL_CHANNELS"] = str(args.rccl_channels)
@@ -239,9 +276,13 @@ def main():
     else:
         ddp = dl.DistributedDataParallel(model, bucket_cap_mb=args.bucket_mb)
 
+    last = {}   # --dump-outputs: the model output of the latest step (a captured step replays into it)
+
     def step():
         opt.zero_grad()
         out = ddp(x)
+        if args.dump_outputs:
+            last["logits"] = out
         if cfg["task"] == "cls":
             loss = crit(out, y)
             backward(loss)
@@ -272,20 +313,27 @@ def main():
         step()
         if i == 0:   # one eager step: weight-gradient reduction launches (graph replays issue none)
             red_per_step = _native().wgrad_reduce_launches() - red0
-    from deeplearning_mpi_amd.utils.profiler import ClockStamps
+    clk = None
+    if args.full:
+        from deeplearning_mpi_amd.utils.profiler import ClockStamps
 
-    clk = ClockStamps(dev)   # in-kernel shader clock over the timed steps (two 1024-wave stamp launches, paired per CU)
+        clk = ClockStamps(dev)   # in-kernel shader clock over the timed steps (two 1024-wave stamp launches, paired per CU)
     comm.barrier()
     sync()
     t0 = time.perf_counter()
-    clk.start()
+    if clk is not None:
+        clk.start()
     for _ in range(args.steps):
         loss = step()
-    clk.stop()
+    if clk is not None:
+        clk.stop()
     comm.barrier()
     sync()
     dt = time.perf_counter() - t0
-    clock = clk.summary()
+    if args.dump_outputs and comm.rank == 0:   # before any untimed extra step touches the weights
+        dump_outputs(args.dump_outputs, {"loss": loss, "logits": last["logits"], "params": model.arena.flat,
+                                         "grads": model.arena.grad})
+    clock = clk.summary() if clk is not None else None
     myclk = torch.tensor([clock["sclk_mhz"] if clock else -1.0], dtype=torch.float64, device=dev)
     allclk = torch.empty(world, dtype=torch.float64, device=dev)
     comm.allgather(allclk, myclk)
@@ -301,7 +349,7 @@ def main():
     ips = global_batch * args.steps / dt
     # N > 1: a few untimed HIP-event-timed steps after the timed region answer "how much all-reduce
     # was left exposed after the backward pass" in the same JSON line
-    if args.breakdown == 0 and (world > 1 or args.rehearse) and not args.graph:
+    if args.full and args.breakdown == 0 and (world > 1 or args.rehearse) and not args.graph:
         args.breakdown = 3
     bd_max = None
     if args.breakdown > 0 and not args.graph:
@@ -389,7 +437,7 @@ def main():
     # how long it ran, its bus bandwidth, and how far the last one ended after the backward's compute
     bucket_info = None
     bc = getattr(ddp, "_bucket_comm", None)
-    if args.bucket_probe and not args.graph and bc is not None and hasattr(bc, "set_timing"):
+    if args.full and args.bucket_probe and not args.graph and bc is not None and hasattr(bc, "set_timing"):
         bc.set_timing(True)
         step()
         sync()

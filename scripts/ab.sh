@@ -17,7 +17,7 @@ for i in $(seq 1 ${REPS:-3}); do
     for c in ${CONFIGS:-resnet50}; do
       log=$O/${c}_${name}_$i.log
       env $(echo $envs | tr ',' ' ') timeout -k 10 ${TLIM:-300} python bench.py --config $c --steps ${STEPS:-20} \
-        --warmup ${WARMUP:-5} $args > $log 2>&1 || { echo "fail $name $c"; tail -5 $log; exit 1; }
+        --warmup ${WARMUP:-5} --full $args > $log 2>&1 || { echo "fail $name $c"; tail -5 $log; exit 1; }
       echo "$c $name #$i $(grep -o '"value": [0-9.]*' $log) $(grep -o '"comm_exposed_ms": [0-9.a-z]*' $log)"
     done
   done

@@ -34,8 +34,8 @@ def _json_lines(out):
 def test_bench_self_launches_n_ranks(launcher):
     if launcher == "mpirun" and not (shutil.which("mpirun") or os.path.exists("/opt/conda/bin/mpirun")):
         pytest.skip("no mpirun")
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--launcher", launcher, *SMALL], cwd=ROOT,
-                       env=_env(), capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--launcher", launcher, "--full", *SMALL],
+                       cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = _json_lines(r.stdout)
     assert len(lines) == 1, r.stdout   # rank 0 only
@@ -57,6 +57,31 @@ def test_bench_single_rank_unchanged():
     assert r.returncode == 0, r.stderr[-3000:]
     (j,) = _json_lines(r.stdout)
     assert j["n_gpus"] == 1 and j["config"]["parallelism"] == "dp1"
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run carries the headline fields and none of the --full instruments; --dump-outputs
+    writes the last timed step's arrays as float32 .npy, 64 MB at the most in all."""
+    import numpy as np
+
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", str(out), *SMALL], cwd=ROOT,
+                       env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    (j,) = _json_lines(r.stdout)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in j
+    assert j["steps"] == 2 and j["ms_per_step"] > 0
+    assert j["value"] == pytest.approx(4 / (j["ms_per_step"] / 1e3), rel=1e-3)
+    assert j["clock"] is None and j["dist"]["bucket_probe"] is None and j["dist"]["comm_exposed_ms"] is None
+    files = sorted(p.name for p in out.iterdir())
+    assert files == ["grads.npy", "logits.npy", "loss.npy", "params.npy"]
+    arrs = {f[:-4]: np.load(out / f) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+    assert sum(a.nbytes for a in arrs.values()) <= 64e6
+    assert arrs["logits"].size == 4 * 10 and arrs["params"].size == arrs["grads"].size > 0
+    assert float(arrs["loss"].reshape(())) == pytest.approx(j["config"]["final_loss"], abs=1e-4)
+    assert np.abs(arrs["grads"]).sum() > 0
 
 
 def test_bench_rejects_world_size_mismatch():

@@ -53,7 +53,7 @@ def test_comm_bench_world1_schema():
 
 def test_bench_rccl1_bucket_probe():
     r = subprocess.run([sys.executable, "bench.py", "--config", "resnet18_cifar", "--steps", "2", "--warmup", "1",
-                        "--rccl1", "1", "--graph", "0"], cwd=ROOT, capture_output=True, text=True, timeout=300)
+                        "--rccl1", "1", "--graph", "0", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     (j,) = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{") and '"metric"' in l]
     d = j["dist"]
