@@ -254,7 +254,7 @@ class NativeBackend:
 
     def wgrad_defer(self, on: bool):
         """Queue weight-gradient split reductions (on) / flush the queue and launch them at once
-        again (off); ops.cpp wgrad_reduce_or_defer."""
+        again (off); conv_bwd.cpp wgrad_reduce_or_defer."""
         self.C.set_wgrad_defer(bool(on))
 
     def wgrad_flush(self):

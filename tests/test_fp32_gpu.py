@@ -94,6 +94,38 @@ def test_conv_fwd_dgrad_wgrad_fp32(shape):
     assert _rel(g, gr) < TOL
 
 
+def test_conv_fwd_bn_fp32_autotuned_fits_conv_mtiles():
+    """fp32 conv + BN statistics + finalize with the tile autotuner on, its statistics buffer sized by
+    conv_mtiles: 4 x 128 x 128, 32 -> 64, 1x1 (static tile 128 rows; the tuner also times 64-row tiles,
+    twice the rows).  Which tile wins is timing-dependent, so this could pass by luck with a bound
+    sized for the static tile; the deterministic proof that the bound covers every tile the tuner may
+    pick is test_conv_plan_cpu.py::test_no_plan_exceeds_the_bound."""
+    nb, rb = _be()
+    N, H, W, Cin, K = 4, 128, 128, 32, 64
+    x, xr = _act(N, H, W, Cin)
+    w = torch.randn(K, 1, 1, Cin, device=DEV) / Cin ** 0.5
+    bias = torch.randn(K, device=DEV)
+    y, yr = _empty(N, H, W, K), _empty(N, H, W, K, F64)
+    str_ = torch.zeros(1, 2, K, device=DEV, dtype=F64)
+    v = torch.empty(4, K, device=DEV)
+    rm, rv = torch.zeros(K, device=DEV), torch.ones(K, device=DEV)
+    nb.C.set_conv_autotune(1)
+    nb.C.clear_conv_plans()
+    try:
+        st = torch.zeros(nb.conv_mtiles(N, H, W, Cin, K, 1, 1, 1, 0), 2, K, device=DEV)
+        nb.conv_fwd_bn(x, w, K, 1, 1, 1, 0, y, bias, st, N * H * W, None, None, rm, rv, 0.1, 1e-5, v[0], v[1], v[2],
+                       v[3])
+        torch.cuda.synchronize()
+    finally:
+        nb.C.set_conv_autotune(-1)
+        nb.C.clear_conv_plans()
+    rb.conv_fwd(xr, w.double(), K, 1, 1, 1, 0, yr, bias=bias.double(), stats=str_)
+    assert _rel(y.buf, yr.buf) < TOL
+    assert _rel(st.double().sum(0)[0], str_[0, 0]) < 1e-4
+    assert _rel(st.double().sum(0)[1], str_[0, 1]) < 1e-4
+    assert _rel(v[2], str_[0, 0] / (N * H * W)) < 1e-4   # the finalize read the rows the launch wrote
+
+
 def test_convT_and_linear_fp32():
     nb, rb = _be()
     N, H, W, Ci, Co = 2, 8, 12, 256, 128
@@ -321,7 +353,7 @@ def test_training_step_every_op_matches_fp64(name):
     print({k: f"{v:.1e}" for k, v in sorted(sh.worst.items())})
     assert sh.calls > 40
     assert not sh.records, sh.records[:5]
-    # the training forward runs conv + BN statistics + finalize as conv_fwd_bn (ops.cpp)
+    # the training forward runs conv + BN statistics + finalize as conv_fwd_bn (conv_fwd.cpp)
     for op in ("conv_fwd_bn", "conv_dgrad", "conv_wgrad", "bn_bwd"):
         assert op in sh.worst
 

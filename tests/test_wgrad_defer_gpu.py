@@ -1,4 +1,4 @@
-"""Deferred, batched weight-gradient split reductions (ops.cpp wgrad_reduce_or_defer, the engine
+"""Deferred, batched weight-gradient split reductions (conv_bwd.cpp wgrad_reduce_or_defer, the engine
 backward's mode) at model level: one training step's parameter gradients are bit-identical to the
 step with every reduction launched right after its weight-gradient GEMM (two launches each), and the
 step issues a handful of reduction launches instead of one or two per convolution."""
