@@ -10,7 +10,9 @@ Deliberate fixes: the NaN/Inf skip is collective (decid
 all-reduced gradient norm on the device, identical on every rank -> no deadlock, no host sync);
 the log and checkpoints are written by global rank 0 only; evaluation uses the unwrapped module.
 Additions: --synthetic, --image_size, --in_channels, --data_dir, --scale, --up_sample_mode,
---backend, --device, --max_norm, --steps_per_epoch, --workers.
+--backend, --device, --max_norm, --steps_per_epoch, --workers, and multi-class masks: --num_classes K > 1
+trains UNet(out_classes=K) on the integer class-index masks with the pixel-wise CrossEntropyLoss
+(--ignore_index) and evaluates the mean foreground Dice of the argmax (ops.dice_multiclass).
 """
 from __future__ import annotations
 
@@ -29,7 +31,7 @@ from tqdm import tqdm
 from .. import parallel
 from ..data import CarvanaDataset, DeviceBatches, DeviceCachedDataset, DistributedSampler, SyntheticMasks
 from ..models import UNet
-from ..ops import BCEWithLogitsLoss, backward, dice_per_sample
+from ..ops import BCEWithLogitsLoss, CrossEntropyLoss, backward, dice_multiclass, dice_per_sample
 from ..optim import Adam, clip_grad_norm_
 from ..utils.graphs import CapturedStep
 from ..utils.checkpoint import load_checkpoint, resume_state, save_checkpoint, set_rng_state
@@ -49,6 +51,11 @@ def build_argparser() -> argparse.ArgumentParser:
     p.add_argument("--synthetic_size", type=int, default=64)
     p.add_argument("--image_size", type=int, default=512)
     p.add_argument("--in_channels", type=int, default=3)
+    p.add_argument("--num_classes", type=int, default=1,
+                   help="1: one logit per pixel, BCEWithLogits on the binarised mask (the reference); K > 1: K "
+                        "logits per pixel, pixel-wise cross-entropy on the mask's class indices")
+    p.add_argument("--ignore_index", type=int, default=-100,
+                   help="label left out of the multi-class loss and Dice (--num_classes > 1)")
     p.add_argument("--data_dir", default="data")
     p.add_argument("--scale", type=float, default=0.2)
     p.add_argument("--up_sample_mode", default="conv_transpose", choices=["conv_transpose", "bilinear"])
@@ -102,13 +109,17 @@ class RankLog:
 
 
 @torch.no_grad()
-def evaluate_model(model, device, test_loader) -> float:
+def evaluate_model(model, device, test_loader, num_classes=1, ignore_index=-100) -> float:
     model.eval()
     scores = []
     for batch in test_loader:
         images = batch["image"].to(device, dtype=torch.float32)
-        masks = batch["mask"].to(device, dtype=torch.float32)
-        scores.append(dice_per_sample(model(images), masks))
+        if num_classes > 1:
+            masks = batch["mask"].to(device, dtype=torch.int64)
+            scores.append(dice_multiclass(model(images), masks, ignore_index))
+        else:
+            masks = batch["mask"].to(device, dtype=torch.float32)
+            scores.append(dice_per_sample(model(images), masks))
     model.train()
     if not scores:
         return 0.0
@@ -118,10 +129,14 @@ def evaluate_model(model, device, test_loader) -> float:
 def build_data_loaders(args, device):
     if args.synthetic:
         ds = SyntheticMasks(args.synthetic_size, (args.in_channels, args.image_size, args.image_size),
-                            seed=args.random_seed)
+                            seed=args.random_seed, num_classes=args.num_classes)
     else:
         ds = CarvanaDataset(images_dir=os.path.join(args.data_dir, "images"),
-                            mask_dir=os.path.join(args.data_dir, "masks"), scale=args.scale)
+                            mask_dir=os.path.join(args.data_dir, "masks"), scale=args.scale,
+                            multiclass=args.num_classes > 1)
+        if args.num_classes > 1 and len(ds.mask_values) > args.num_classes:
+            raise ValueError(f"the masks under {args.data_dir} hold {len(ds.mask_values)} distinct values, more "
+                             f"than --num_classes {args.num_classes}")
     train_size = int(0.8 * len(ds))
     test_size = len(ds) - train_size
     # same split on every rank (seeded generator rather than the global RNG)
@@ -157,7 +172,10 @@ def benchmark(args, train_step, captured, x, y, comm, device) -> dict:
     """--benchmark_steps: synthetic device batch, 3 warm-up steps, timed steps, images/sec."""
     g = torch.Generator(device=device).manual_seed(1234 + comm.rank)
     x.copy_(torch.randn(x.shape, generator=g, device=device))
-    y.copy_((torch.rand(y.shape, generator=g, device=device) > 0.5).float())
+    if args.num_classes > 1:
+        y.copy_(torch.randint(args.num_classes, y.shape, generator=g, device=device))
+    else:
+        y.copy_((torch.rand(y.shape, generator=g, device=device) > 0.5).float())
     step = captured if captured is not None else (lambda: train_step(x, y))
     for _ in range(3):
         step()
@@ -181,6 +199,8 @@ def benchmark(args, train_step, captured, x, y, comm, device) -> dict:
 
 
 def run(args) -> dict:
+    if args.num_classes < 1:   # (callers that build the namespace themselves)
+        raise ValueError(f"--num_classes must be >= 1, got {args.num_classes}")
     comm = parallel.init_distributed(args.backend)
     rank, world, local_rank = comm.rank, comm.world_size, comm.local_rank
     device = comm.device if args.device == "auto" else torch.device(args.device)
@@ -194,12 +214,14 @@ def run(args) -> dict:
     log(f"World size: {world}, Local rank: {local_rank}, GPU: {gpu}")
 
     train_loader, test_loader, sampler = build_data_loaders(args, device)
-    model = UNet(out_classes=1, up_sample_mode=args.up_sample_mode, in_channels=args.in_channels).to(device)
+    K = args.num_classes
+    mask_dtype = torch.int64 if K > 1 else torch.float32
+    model = UNet(out_classes=K, up_sample_mode=args.up_sample_mode, in_channels=args.in_channels).to(device)
     model.precision = args.precision
     ddp = parallel.DistributedDataParallel(model, bucket_cap_mb=args.bucket_mb)
     model_filepath = os.path.join(args.model_dir, args.model_filename)
     optimizer = Adam(model.parameters(), lr=args.learning_rate)
-    criterion = BCEWithLogitsLoss()
+    criterion = CrossEntropyLoss(ignore_index=args.ignore_index) if K > 1 else BCEWithLogitsLoss()
     start_epoch = 0
     if args.resume:
         # weights (reference layout) + the sidecar: Adam moments and step, next epoch, RNG states
@@ -210,7 +232,9 @@ def run(args) -> dict:
                            comm_backend=getattr(comm, "backend", "single"))
 
     def train_step(images, masks):
-        pred = ddp(images).squeeze(1)
+        pred = ddp(images)
+        if K == 1:
+            pred = pred.squeeze(1)
         loss = criterion(pred, masks)
         optimizer.zero_grad()
         backward(loss)
@@ -221,7 +245,7 @@ def run(args) -> dict:
 
     S = args.image_size
     x_static = torch.zeros(args.batch_size, args.in_channels, S, S, device=device)
-    y_static = torch.zeros(args.batch_size, S, S, device=device)
+    y_static = torch.zeros(args.batch_size, S, S, dtype=mask_dtype, device=device)
     captured = None
     if args.graph and device.type == "cuda":
         captured = CapturedStep(lambda: train_step(x_static, y_static), warmup=2, inputs=(x_static, y_static),
@@ -243,7 +267,7 @@ def run(args) -> dict:
                        disable=rank != 0 or not sys.stderr.isatty())   # no per-step host sync for a loss postfix
             for batch in bar:
                 images = batch["image"].to(device, dtype=torch.float32, non_blocking=True)
-                masks = batch["mask"].to(device, dtype=torch.float32, non_blocking=True)
+                masks = batch["mask"].to(device, dtype=mask_dtype, non_blocking=True)
                 if captured is not None and images.shape == x_static.shape:
                     captured.set_inputs(images, masks)
                     loss = captured()
@@ -259,7 +283,7 @@ def run(args) -> dict:
             log(f"Epoch {epoch + 1} | Loss: {avg_loss:.4f} | Duration: {time.time() - t0:.2f}s")
             if (epoch + 1) % args.eval_every == 0 and rank == 0:
                 state = resume_state(epoch + 1)   # epoch-boundary RNG states, taken before evaluating
-                dice = evaluate_model(model, device, test_loader)
+                dice = evaluate_model(model, device, test_loader, K, args.ignore_index)
                 save_checkpoint(ddp, model_filepath, optimizer=optimizer, extra=state, rank=rank)
                 print("-" * 75)
                 print(f"Epoch {epoch + 1} Dice Score: {dice:.4f}")
@@ -269,7 +293,7 @@ def run(args) -> dict:
         if rank == 0:
             print("\n" + "=" * 80 + "\nTRAINING COMPLETED - FINAL EVALUATION\n" + "=" * 80)
             state = resume_state(args.num_epochs)
-            final = evaluate_model(model, device, test_loader)
+            final = evaluate_model(model, device, test_loader, K, args.ignore_index)
             save_checkpoint(ddp, model_filepath, optimizer=optimizer, extra=state, rank=rank)
             print(f"FINAL DICE COEFFICIENT: {final:.4f}\n" + "=" * 80 + "\n")
             log("=" * 80)
@@ -286,5 +310,13 @@ def run(args) -> dict:
     return history
 
 
+def parse_args(argv=None):
+    p = build_argparser()
+    args = p.parse_args(argv)
+    if args.num_classes < 1:
+        p.error(f"--num_classes must be >= 1, got {args.num_classes}")
+    return args
+
+
 def main(argv=None):
-    return run(build_argparser().parse_args(argv))
+    return run(parse_args(argv))

@@ -75,6 +75,7 @@ c10::optional<at::Tensor> conv2d_dgrad_pro(const at::Tensor& dy, int N, int P, i
     throw std::runtime_error("conv2d_dgrad: fused BN tensors must be 8-channel aligned");
   g_ran.dgrad_stream = 0;
   g_ran.conv3 = 0;
+  if (R == 1 && S == 1 && K == 8) g_ran.head_dgrad = 0;   // a padded-K head's data gradient through the GEMM
   {  // streaming 3x3 data gradient (conv3x3_stream.hip, 64 -> 64): a forward conv of dy with wT, taps flipped
     const int mode = a.mscale ? 2 : 0;
     int th, tw, G;
@@ -453,6 +454,7 @@ void register_conv_bwd(pybind11::module& m) {
   def_int(m, "set_wgrad3_blocks", nullptr, &g_sw.wgrad3_blocks);
   def_int(m, "set_wgrad_blocks", nullptr, &g_sw.wgrad_blocks);
   def_int(m, nullptr, "dgrad_stream_last", &g_ran.dgrad_stream);
+  def_int(m, nullptr, "head_dgrad_last", &g_ran.head_dgrad);
 }
 
 }  // namespace dlmpi_ext

@@ -498,6 +498,8 @@ void conv1x1_head_affine(const at::Tensor& z, int N, int H, int W, int C, int ld
   if (act_f32(z, "conv1x1_head_affine") || !dlmpi_head1x1_ok(C, kv) || ldz % 8 || zoff % 8 ||
       scale.numel() < C || shift.numel() < C || (y.scalar_type() != at::kFloat && y.scalar_type() != at::kBFloat16))
     throw std::runtime_error("conv1x1_head_affine: bf16 z, C in 16..512, <= 4 outputs, aligned rows");
+  if (ldw < C || w.numel() < (int64_t)(kv - 1) * ldw + C)
+    throw std::runtime_error("conv1x1_head_affine: weight rows [kv][ldw] reach outside w");
   check(dlmpi_head1x1(z.data_ptr(), ldz, zoff, (int64_t)N * H * W, C, w.data_ptr(), ldw, optr<float>(bias),
                       y.data_ptr(), ldy, yoff, kv, y.scalar_type() == at::kFloat ? 1 : 0, ptr<float>(scale),
                       ptr<float>(shift), cur_stream()),

@@ -156,6 +156,31 @@ at::Tensor outer_dgrad_bn(const at::Tensor& dy, int lddy, int64_t M, int C, cons
         "outer_dgrad_bn");
   return part;
 }
+// the same for a 1x1 convolution with K = 2..4 output channels (the multi-class UNet head): dl [M][lddl],
+// w [C][ldw] with the K class weights of a channel first in its row
+at::Tensor head_dgrad_bn(const at::Tensor& dl, int lddl, int K, int64_t M, int C, const at::Tensor& w, int ldw,
+                         const at::Tensor& z, const at::Tensor& mscale, const at::Tensor& mshift, at::Tensor dx) {
+  require_gpu(dl, "dl");
+  if (K < 2 || K > 4 || C < 8 || C % 8 || C > 2048 || M < 1 || lddl < K || ldw < K)
+    throw std::runtime_error("head_dgrad_bn: 2 <= K <= 4, C a multiple of 8 up to 2048, lddl / ldw >= K");
+  same_type(dl, w, "head_dgrad_bn w");
+  same_type(dl, z, "head_dgrad_bn z");
+  same_type(dl, dx, "head_dgrad_bn dx");
+  if (dl.numel() < (M - 1) * lddl + K || w.numel() < (int64_t)(C - 1) * ldw + K || z.numel() < M * C ||
+      dx.numel() < M * C || mscale.numel() < C || mshift.numel() < C || mscale.scalar_type() != at::kFloat ||
+      mshift.scalar_type() != at::kFloat || !dl.is_contiguous() || !w.is_contiguous() || !z.is_contiguous() ||
+      !dx.is_contiguous())
+    throw std::runtime_error("head_dgrad_bn: operand sizes");
+  const int64_t rpb = 256 / (C / 8);
+  const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (M + rpb * 8 - 1) / (rpb * 8)));
+  at::Tensor part = at::empty({nblk, 2, C}, dl.options().dtype(at::kFloat));
+  check(dlmpi_head_dgrad_bn(dl.data_ptr(), lddl, K, M, C, w.data_ptr(), ldw, z.data_ptr(), ptr<float>(mscale),
+                            ptr<float>(mshift), dx.data_ptr(), ptr<float>(part), nblk, act_f32(dl, "head_dgrad_bn"),
+                            cur_stream()),
+        "head_dgrad_bn");
+  g_ran.head_dgrad = 1;
+  return part;
+}
 // max-pool backward fused with the BN-backward statistics of the producing BN+ReLU (mask from z);
 // returns the partials [nblk][2][C] for bn_bwd_finalize_fused
 at::Tensor maxpool_bwd_bn(const at::Tensor& dy, const at::Tensor& idx, int N, int H, int W, int C, int k, int stride,
@@ -247,6 +272,78 @@ void argmax_correct(const at::Tensor& logits, int ldl, const at::Tensor& labels,
 }
 void dice(const at::Tensor& logits, int ldl, const at::Tensor& target, int N, int64_t HW, at::Tensor out) {
   check(dlmpi_dice(ptr<float>(logits), ldl, ptr<float>(target), N, HW, ptr<float>(out), cur_stream()), "dice");
+}
+
+// Pixel-wise losses / counts (pixel_ce.hip): t is addressed as n*sn + k*sk + p*sp over N x K x HW; every
+// address must lie inside its storage, the labels are int64 [N*HW].
+static void pix_check(const at::Tensor& t, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                      const at::Tensor& labels, const char* what) {
+  require_gpu(t, what);
+  if (t.scalar_type() != at::kFloat || N < 1 || K < 2 || K > 256 || HW < 1 || sn < 0 || sk < 0 || sp < 0)
+    throw std::runtime_error(std::string(what) + ": fp32 logits, 2 <= K <= 256, non-negative strides");
+  const int64_t last = (N - 1) * sn + (K - 1) * sk + (HW - 1) * sp;
+  const int64_t avail = (int64_t)(t.storage().nbytes() / sizeof(float)) - t.storage_offset();
+  if (last >= avail) throw std::runtime_error(std::string(what) + ": strides reach outside the tensor's storage");
+  if (labels.scalar_type() != at::kLong || !labels.is_contiguous() || labels.numel() != (int64_t)N * HW ||
+      !labels.is_cuda())
+    throw std::runtime_error(std::string(what) + ": labels must be contiguous int64 [N*HW] on the GPU");
+}
+static void pix_weight_check(const c10::optional<at::Tensor>& weight, int K, const char* what) {
+  if (weight && weight->defined() &&
+      (weight->scalar_type() != at::kFloat || !weight->is_contiguous() || weight->numel() != K || !weight->is_cuda()))
+    throw std::runtime_error(std::string(what) + ": weight must be contiguous fp32 [K] on the GPU");
+}
+static void f32_numel(const at::Tensor& t, int64_t n, const char* what) {
+  if (t.scalar_type() != at::kFloat || !t.is_contiguous() || t.numel() != n || !t.is_cuda())
+    throw std::runtime_error(std::string(what) + ": contiguous fp32 GPU tensor of " + std::to_string(n) + " elements");
+}
+
+void pixel_ce_fwd(const at::Tensor& logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                  const at::Tensor& labels, int64_t ignore_index, const c10::optional<at::Tensor>& weight,
+                  at::Tensor lse, at::Tensor loss, at::Tensor den) {
+  pix_check(logits, sn, sk, sp, N, K, HW, labels, "pixel_ce_fwd");
+  pix_weight_check(weight, K, "pixel_ce_fwd");
+  f32_numel(lse, (int64_t)N * HW, "pixel_ce_fwd lse");
+  f32_numel(loss, 1, "pixel_ce_fwd loss");
+  f32_numel(den, 1, "pixel_ce_fwd den");
+  at::Tensor partial = at::empty({dlmpi_pixel_ce_blocks((int64_t)N * HW), 2}, logits.options());
+  check(dlmpi_pixel_ce_fwd(ptr<float>(logits), sn, sk, sp, N, K, HW, ptr<int64_t>(labels), ignore_index,
+                           optr<float>(weight), ptr<float>(lse), ptr<float>(partial), ptr<float>(loss),
+                           ptr<float>(den), cur_stream()),
+        "pixel_ce_fwd");
+}
+void pixel_ce_bwd(const at::Tensor& logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                  const at::Tensor& labels, int64_t ignore_index, const c10::optional<at::Tensor>& weight,
+                  const at::Tensor& lse, const c10::optional<at::Tensor>& go, const at::Tensor& den,
+                  at::Tensor dlogits) {
+  pix_check(logits, sn, sk, sp, N, K, HW, labels, "pixel_ce_bwd");
+  pix_check(dlogits, sn, sk, sp, N, K, HW, labels, "pixel_ce_bwd dlogits");
+  pix_weight_check(weight, K, "pixel_ce_bwd");
+  f32_numel(lse, (int64_t)N * HW, "pixel_ce_bwd lse");
+  f32_numel(den, 1, "pixel_ce_bwd den");
+  if (go && go->defined()) f32_numel(*go, 1, "pixel_ce_bwd go");
+  check(dlmpi_pixel_ce_bwd(ptr<float>(logits), sn, sk, sp, N, K, HW, ptr<int64_t>(labels), ignore_index,
+                           optr<float>(weight), ptr<float>(lse), optr<float>(go), ptr<float>(den),
+                           ptr<float>(dlogits), cur_stream()),
+        "pixel_ce_bwd");
+}
+void seg_counts(const at::Tensor& logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                const at::Tensor& labels, int64_t ignore_index, at::Tensor counts) {
+  pix_check(logits, sn, sk, sp, N, K, HW, labels, "seg_counts");
+  if (counts.scalar_type() != at::kLong || !counts.is_contiguous() || counts.numel() != (int64_t)N * K * 3 ||
+      !counts.is_cuda())
+    throw std::runtime_error("seg_counts: counts must be contiguous int64 [N][K][3] on the GPU");
+  check(dlmpi_seg_counts(ptr<float>(logits), sn, sk, sp, N, K, HW, ptr<int64_t>(labels), ignore_index,
+                         ptr<int64_t>(counts), cur_stream()),
+        "seg_counts");
+}
+// channels-last loss gradient x [M][K] fp32 -> y [M][Kp] activations, zero-padded
+void nhwc_pad_cast(const at::Tensor& x, int64_t M, int K, int Kp, at::Tensor y) {
+  f32_numel(x, M * K, "nhwc_pad_cast x");
+  require_gpu(y, "y");
+  if (!y.is_contiguous() || y.numel() != M * Kp) throw std::runtime_error("nhwc_pad_cast: y must be contiguous [M][Kp]");
+  check(dlmpi_nhwc_pad_cast(ptr<float>(x), M, K, Kp, y.data_ptr(), act_f32(y, "nhwc_pad_cast"), cur_stream()),
+        "nhwc_pad_cast");
 }
 
 // --------------------------------- optimizers ----------------------------------------------
@@ -364,6 +461,8 @@ void register_ops(pybind11::module& m) {
   m.def("maxpool_bwd", &maxpool_bwd);
   m.def("maxpool_bwd_bn", &maxpool_bwd_bn);
   m.def("outer_dgrad_bn", &outer_dgrad_bn);
+  m.def("head_dgrad_bn", &head_dgrad_bn);
+  m.def("nhwc_pad_cast", &nhwc_pad_cast);
   m.def("avgpool_fwd", &avgpool_fwd);
   m.def("avgpool_bwd", &avgpool_bwd);
   m.def("nchw_to_nhwc", &nchw_to_nhwc);
@@ -378,6 +477,10 @@ void register_ops(pybind11::module& m) {
   m.def("bce_bwd", &bce_bwd);
   m.def("argmax_correct", &argmax_correct);
   m.def("dice", &dice);
+  m.def("pixel_ce_fwd", &pixel_ce_fwd);
+  m.def("set_pixel_tiles", [](int on) { dlmpi_set_pixel_tiles(on); });
+  m.def("pixel_ce_bwd", &pixel_ce_bwd);
+  m.def("seg_counts", &seg_counts);
   m.def("sgd_step", &sgd_step);
   m.def("adam_step", &adam_step);
   m.def("grad_norm", &grad_norm);

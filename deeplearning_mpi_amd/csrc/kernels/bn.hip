@@ -194,6 +194,54 @@ __global__ __launch_bounds__(256) void outer_dgrad_bn_kernel(const T* __restrict
   block_combine<2>(acc, rm, C, partial);
 }
 
+// The same for a 1x1 convolution with K = 2..4 output channels (the multi-class UNet head):
+// dx[m, c] = [z*scale + shift > 0] * sum_k dl[m, k] * w[c, k], summed in fp32 in ascending k.  The GEMM
+// path pads the reduction from K to 8; here a row costs K broadcast loads of dl beside the z read and
+// the dx write.  Same row map, partial layout [blocks][2][C] and finalize as the K = 1 kernel.
+template <int K, typename T>
+__global__ __launch_bounds__(256) void head_dgrad_bn_kernel(const T* __restrict__ dl, int lddl, int64_t M, int C,
+                                                            const T* __restrict__ w, int ldw,
+                                                            const T* __restrict__ z,
+                                                            const float* __restrict__ msc,
+                                                            const float* __restrict__ msh,
+                                                            T* __restrict__ dx, float* __restrict__ partial) {
+  const RowMap rm = rowmap(C);
+  float acc[2][8] = {};
+  if (rm.active) {
+    const int c0 = rm.cc * 8;
+    float wv[K][8], sc[8], sh[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) wv[k][e] = load1(w + (int64_t)(c0 + e) * ldw + k);
+      sc[e] = msc[c0 + e];
+      sh[e] = msh[c0 + e];
+    }
+    for (int64_t row = (int64_t)blockIdx.x * rm.RPB + rm.rr; row < M; row += (int64_t)gridDim.x * rm.RPB) {
+      float d[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) d[k] = load1(dl + row * lddl + k);
+      float zz[8], g[8];
+      load8(z + row * C + c0, zz);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        float a = d[0] * wv[0][e];
+#pragma unroll
+        for (int k = 1; k < K; ++k) a += d[k] * wv[k][e];
+        g[e] = zz[e] * sc[e] + sh[e] > 0.f ? a : 0.f;
+      }
+      store8(dx + row * C + c0, g);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float r = stored<T>(g[e]);
+        acc[0][e] += r;
+        acc[1][e] += r * zz[e];
+      }
+    }
+  }
+  block_combine<2>(acc, rm, C, partial);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void bn_stats_kernel(const T* __restrict__ x, int64_t M, int C, int ldx,
                                                        int xoff, float* __restrict__ partial) {
@@ -728,6 +776,31 @@ extern "C" hipError_t dlmpi_outer_dgrad_bn(const void* dy, int lddy, int64_t M, 
   if (C % 8 || C > 2048 || M <= 0) return hipErrorInvalidValue;
   LAUNCH_TLAUNCH(outer_dgrad_bn_kernel, dim3(nblk), CT(dy), lddy, M, C, CT(w), ldw, CT(z), mscale, mshift, MT(dx),
                 partial);
+  return hipGetLastError();
+}
+
+// dl [M][lddl] (columns 0..K-1 read), w [C][ldw] (w[c][k] = the head weight of class k, channel c)
+extern "C" hipError_t dlmpi_head_dgrad_bn(const void* dl, int lddl, int K, int64_t M, int C, const void* w, int ldw,
+                                          const void* z, const float* mscale, const float* mshift, void* dx,
+                                          float* partial, int nblk, int f32, hipStream_t s) {
+  if (C % 8 || C > 2048 || M <= 0 || K < 2 || K > 4 || lddl < K || ldw < K || nblk < 1) return hipErrorInvalidValue;
+#define HEAD_DGRAD_K(K_)                                                                                     \
+  case K_:                                                                                                   \
+    if (f32)                                                                                                 \
+      hipLaunchKernelGGL((head_dgrad_bn_kernel<K_, float>), dim3(nblk), dim3(256), 0, s, (const float*)dl,   \
+                         lddl, M, C, (const float*)w, ldw, (const float*)z, mscale, mshift, (float*)dx,      \
+                         partial);                                                                           \
+    else                                                                                                     \
+      hipLaunchKernelGGL((head_dgrad_bn_kernel<K_, uint16_t>), dim3(nblk), dim3(256), 0, s,                  \
+                         (const uint16_t*)dl, lddl, M, C, (const uint16_t*)w, ldw, (const uint16_t*)z,       \
+                         mscale, mshift, (uint16_t*)dx, partial);                                            \
+    break;
+  switch (K) {
+    HEAD_DGRAD_K(2)
+    HEAD_DGRAD_K(3)
+    HEAD_DGRAD_K(4)
+  }
+#undef HEAD_DGRAD_K
   return hipGetLastError();
 }
 

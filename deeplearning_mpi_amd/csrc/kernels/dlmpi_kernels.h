@@ -363,6 +363,12 @@ hipError_t dlmpi_maxpool_bwd_bn(const void* dy, const uint8_t* idx, int N, int H
 hipError_t dlmpi_outer_dgrad_bn(const void* dy, int lddy, int64_t M, int C, const void* w, int ldw, const void* z,
                                 const float* mscale, const float* mshift, void* dx, float* partial, int nblk, int f32,
                                 hipStream_t s);
+// the same for K = 2..4 output channels (the multi-class head): dx[m,c] = sum_k dl[m*lddl + k] * w[c*ldw + k]
+hipError_t dlmpi_head_dgrad_bn(const void* dl, int lddl, int K, int64_t M, int C, const void* w, int ldw,
+                               const void* z, const float* mscale, const float* mshift, void* dx, float* partial,
+                               int nblk, int f32, hipStream_t s);
+// x [M][K] fp32 (a channels-last loss gradient) -> y [M][Kp] storage type, zero-padded (pixel_ce.hip)
+hipError_t dlmpi_nhwc_pad_cast(const float* x, int64_t M, int K, int Kp, void* y, int f32, hipStream_t s);
 // per-(device, stream role) split-K workspaces for the conv kernel (bn.hip): an fp32 slab of at least
 // `floats` elements and `n` zeroed self-resetting tickets; null if unavailable (e.g. would have to
 // grow during a graph capture)
@@ -403,12 +409,28 @@ hipError_t dlmpi_bce_fwd(const float* logits, int ldl, const float* target, int6
 hipError_t dlmpi_bce_bwd(const float* logits, int ldl, const float* target, int64_t M, const float* go, float scale,
                          float* dlogits, hipStream_t s);
 hipError_t dlmpi_sum_f32(const float* x, int64_t n, float* out, float scale, hipStream_t s);
+// pixel-wise softmax cross-entropy over N x HW pixels and K = 2..256 classes (pixel_ce.hip): logits fp32 at
+// n*sn + k*sk + p*sp (elements), labels int64 [N*HW] (ignore_index or outside [0, K): ignored), weight
+// fp32 [K] or null; lse [N*HW], partial [dlmpi_pixel_ce_blocks(N*HW)][2], loss = sum w nll / sum w, den = sum w
+int dlmpi_pixel_ce_blocks(int64_t M);
+void dlmpi_set_pixel_tiles(int on);   // 0: no LDS-tile kernels for class-last logits with K > 4 (A/B)
+hipError_t dlmpi_pixel_ce_fwd(const float* logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                              const int64_t* labels, int64_t ignore_index, const float* weight, float* lse,
+                              float* partial, float* loss, float* den, hipStream_t s);
+// dlogits in the strides of logits: (softmax - onehot) * w[t] * go / den, exact zeros at ignored pixels
+hipError_t dlmpi_pixel_ce_bwd(const float* logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                              const int64_t* labels, int64_t ignore_index, const float* weight, const float* lse,
+                              const float* go, const float* den, float* dlogits, hipStream_t s);
 
 // eval
 hipError_t dlmpi_argmax_correct(const float* logits, int ldl, const int64_t* labels, int N, int K, int* correct,
                                 hipStream_t s);
 hipError_t dlmpi_dice(const float* logits, int ldl, const float* target, int N, int64_t HW, float* dice,
                       hipStream_t s);
+// counts int64 [N][K][3] = {|pred = c and target = c|, |pred = c|, |target = c|}, pred = argmax (lowest index
+// on ties), ignored pixels nowhere; zeroed on the stream first
+hipError_t dlmpi_seg_counts(const float* logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                            const int64_t* labels, int64_t ignore_index, int64_t* counts, hipStream_t s);
 
 // optimizers on flat fp32 buffers
 hipError_t dlmpi_sgd(float* p, const float* g, float* m, int64_t n, float lr, float momentum, float dampening,

@@ -39,8 +39,10 @@ class SyntheticImages(Dataset):
 
 
 class SyntheticMasks(Dataset):
-    def __init__(self, n=64, shape=(3, 512, 512), seed=0):
-        self.n, self.shape, self.seed = n, shape, seed
+    """num_classes > 1: int64 class indices uniform in [0, num_classes) instead of the float 0/1 mask."""
+
+    def __init__(self, n=64, shape=(3, 512, 512), seed=0, num_classes=1):
+        self.n, self.shape, self.seed, self.num_classes = n, shape, seed, num_classes
 
     def __len__(self):
         return self.n
@@ -48,7 +50,10 @@ class SyntheticMasks(Dataset):
     def __getitem__(self, i):
         g = torch.Generator().manual_seed(self.seed * 1000003 + i)
         img = torch.rand(self.shape, generator=g)
-        mask = (torch.rand(self.shape[1:], generator=g) > 0.5).float()
+        if self.num_classes > 1:
+            mask = torch.randint(self.num_classes, self.shape[1:], generator=g)
+        else:
+            mask = (torch.rand(self.shape[1:], generator=g) > 0.5).float()
         return {"image": img, "mask": mask}
 
 
@@ -242,11 +247,13 @@ class SegmentationDataset(Dataset):
     * ``cache=True`` decodes each sample once and keeps the tensors (the device-resident variant is
       ``data.DeviceCachedDataset``).
 
-    Returns ``{'image': float32 [C, H, W], 'mask': float32 [H, W]}``."""
+    Returns ``{'image': float32 [C, H, W], 'mask': float32 [H, W]}``; with ``multiclass=True`` the mask
+    is the int64 class-index map itself (``mask_indices``; ``len(mask_values)`` classes)."""
 
-    def __init__(self, images_dir, mask_dir, scale=1.0, mask_suffix="", cache=False, workers=None):
+    def __init__(self, images_dir, mask_dir, scale=1.0, mask_suffix="", cache=False, workers=None, multiclass=False):
         if not 0 < scale <= 1:
             raise ValueError(f"scale must be in (0, 1], got {scale}")
+        self.multiclass = bool(multiclass)
         self.images_dir, self.mask_dir = str(images_dir), str(mask_dir)
         self.scale, self.mask_suffix = float(scale), mask_suffix
         self._pairs = self._pair_files()
@@ -324,7 +331,10 @@ class SegmentationDataset(Dataset):
         if bool((chw > 1).any()):
             chw = chw / 255.0
         image = torch.tensor(chw).float()
-        target = torch.from_numpy(self.mask_indices(mask) > 0).float()
+        if self.multiclass:   # the class indices themselves (int64), for the pixel-wise cross-entropy
+            target = torch.from_numpy(self.mask_indices(mask))
+        else:
+            target = torch.from_numpy(self.mask_indices(mask) > 0).float()
         return {"image": image.contiguous(), "mask": target.contiguous()}
 
     def __len__(self):

@@ -103,6 +103,9 @@ _STREAM_HOLD = True
 
 # One-output-channel 1x1 data gradients as a streaming outer product (bn.hip outer_dgrad_bn_kernel).
 _OUTER_DGRAD = True
+# The same for 2..4 output channels (the multi-class UNet head, bn.hip head_dgrad_bn_kernel); False: the
+# GEMM data gradient with its reduction padded from K to 8 (A/B).
+_HEAD_DGRAD = True
 
 # BN-backward apply of a unit whose input needs no gradient (the ResNet stem, UNet's first conv) is
 # rebuilt in its weight-gradient GEMM's operand prologue instead of stored (ops.act.Deferred).
@@ -540,6 +543,12 @@ class ConvUnit:
                 and hasattr(be, "outer_dgrad_bn") and _OUTER_DGRAD):
             # one output channel (the UNet head): the data gradient is an outer product
             part = be.outer_dgrad_bn(be.materialize(dz), ar.get_compute(self.h_dg), self.Kp, dx, fuse_next)
+            return dx, part
+        if (2 <= self.K <= 4 and self.R == 1 and self.S == 1 and self.stride == 1 and dx_res is None and not colsum
+                and fuse_next is not None and fuse_next.scale is not None and fuse_next.z2 is None
+                and hasattr(be, "head_dgrad_bn") and _HEAD_DGRAD):
+            # a few output channels (the multi-class UNet head): streamed, no reduction padded to 8
+            part = be.head_dgrad_bn(be.materialize(dz), self.K, ar.get_compute(self.h_dg), self.Kp, dx, fuse_next)
             return dx, part
         part = be.conv_dgrad(dz, ar.get_compute(self.h_dg), self.Cp, self.R, self.S, self.stride, self.pad, dx,
                              res=dx_res, fuse=fuse_next, colsum=colsum)

@@ -69,11 +69,24 @@ def replace_poisoned_aux_streams() -> int:
     return n
 
 
+def pixel_strides(x: torch.Tensor):
+    """(sample, class, pixel) element strides of [N, K, H, W] logits in one of the two layouts the pixel
+    kernels address in place -- contiguous NCHW, or an NHWC buffer viewed as NCHW (the engine's
+    output) -- else None."""
+    N, K, H, W = x.shape
+    if x.is_contiguous():
+        return K * H * W, H * W, 1
+    if x.permute(0, 2, 3, 1).is_contiguous():
+        return H * W * K, 1, K
+    return None
+
+
 class NativeBackend:
     name = "native"
     use_side_stream = True     # False: weight gradients on the current stream (A/B)
     use_branch_stream = True   # False: the ResNet downsample branch on the current stream (A/B)
     dt = torch.float32
+    pad_cast_calls = 0         # nchw_to_nhwc calls served by the channels-last pad-cast (tests)
 
     def __init__(self, device, act_dtype=torch.bfloat16):
         from .._ext import native
@@ -163,7 +176,9 @@ class NativeBackend:
                 and 0 < kvalid <= 4 and res is None and scale is None and not relu and stats is None
                 and not self.f32 and x.C in (16, 32, 64, 128, 256, 512) and self.C.head1x1_on()):
             z = x.src
-            self.C.conv1x1_head_affine(z.buf, z.N, z.H, z.W, z.C, z.ld, z.off, w, w.shape[-1], int(kvalid), x.k0,
+            # w is the flat [K][1][1][C] compute copy: its row stride is C (w.shape[-1], the whole slice's
+            # length, sent every class after the first to weights outside this layer)
+            self.C.conv1x1_head_affine(z.buf, z.N, z.H, z.W, z.C, z.ld, z.off, w, z.C, int(kvalid), x.k0,
                                        x.k1, y.buf, y.ld, y.off, bias)
             return 0
         x = self.materialize(x)
@@ -366,6 +381,14 @@ class NativeBackend:
         return self.C.outer_dgrad_bn(dy.buf[:, dy.off:], dy.ld, dx.rows, dx.C, wT, ldw, fuse.z.buf, fuse.scale,
                                      fuse.shift, dx.buf)
 
+    def head_dgrad_bn(self, dl: Act, K, wT, ldw, dx: Act, fuse):
+        """outer_dgrad_bn for a 1x1 conv with K = 2..4 output channels (the multi-class head):
+        dx[m, c] = sum_k dl[m, k] * wT[c * ldw + k], masked by relu(BN(z)); BN-backward partials."""
+        assert fuse.scale is not None and fuse.z2 is None and fuse.mask is None and fuse.mbits is None
+        assert dx.ld == dx.C and dx.off == 0 and fuse.z.ld == fuse.z.C and fuse.z.off == 0 and dl.off == 0
+        return self.C.head_dgrad_bn(dl.buf, dl.ld, int(K), dx.rows, dx.C, wT, ldw, fuse.z.buf, fuse.scale, fuse.shift,
+                                    dx.buf)
+
     def avgpool_fwd(self, x: Act, y: Act):
         self.C.avgpool_fwd(x.buf, x.N, x.H * x.W, x.C, y.buf)
 
@@ -374,6 +397,16 @@ class NativeBackend:
 
     def nchw_to_nhwc(self, x: torch.Tensor, Cpad) -> Act:
         N, Cc, H, W = x.shape
+        if Cc > 1 and x.permute(0, 2, 3, 1).is_contiguous():
+            # channels-last already (the pixel loss's gradient of the engine's own logits): pad + cast
+            # in one launch instead of a copy to NCHW and the transpose back.  Keyed on the layout alone,
+            # so a channels-last model input (or a contiguous [N, C, 1, 1] one) comes here as well: the
+            # same values from another kernel, and pad_cast_calls counts those calls too.
+            x = x.to(self.dt)
+            y = Act.empty(N, H, W, Cpad, self.act_dtype, x.device)
+            self.C.nhwc_pad_cast(x.permute(0, 2, 3, 1), N * H * W, Cc, Cpad, y.buf)
+            self.pad_cast_calls += 1
+            return y
         x = x.contiguous().to(self.dt)
         y = Act.empty(N, H, W, Cpad, self.act_dtype, x.device)
         self.C.nchw_to_nhwc(x, N, Cc, H, W, Cpad, y.buf)
@@ -428,6 +461,34 @@ class NativeBackend:
         d = torch.empty(N, K, dtype=torch.float32, device=logits.device)
         self.C.softmax_ce_bwd(logits, logits.stride(0), labels, lse, N, K, K, go, 1.0 / N, d)
         return d
+
+    def pixel_ce_fwd(self, logits, labels, weight=None, ignore_index=-100):
+        """logits fp32 [N, K, H, W] in one of the two native layouts (pixel_strides), labels int64
+        [N, H, W] -> (loss, per-pixel logsumexp [N*H*W], sum of the kept pixels' weights)."""
+        N, K, H, W = logits.shape
+        st = pixel_strides(logits)
+        dev = logits.device
+        lse = torch.empty(N * H * W, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        den = torch.empty(1, dtype=torch.float32, device=dev)
+        self.C.pixel_ce_fwd(logits, *st, N, K, H * W, labels, int(ignore_index), weight, lse, loss, den)
+        return loss, lse, den
+
+    def pixel_ce_bwd(self, logits, labels, lse, den, go, weight=None, ignore_index=-100):
+        """dlogits in the strides of logits, scaled by go / den on the device."""
+        N, K, H, W = logits.shape
+        d = torch.empty_like(logits)   # dense input: same strides
+        assert d.stride() == logits.stride(), (d.stride(), logits.stride())
+        self.C.pixel_ce_bwd(logits, *pixel_strides(logits), N, K, H * W, labels, int(ignore_index), weight, lse, go,
+                            den, d)
+        return d
+
+    def seg_counts(self, logits, labels, ignore_index=-100):
+        """int64 [N, K, 3]: per sample and class {|pred = c and target = c|, |pred = c|, |target = c|}."""
+        N, K, H, W = logits.shape
+        out = torch.empty(N, K, 3, dtype=torch.int64, device=logits.device)
+        self.C.seg_counts(logits, *pixel_strides(logits), N, K, H * W, labels, int(ignore_index), out)
+        return out
 
     def bce_fwd(self, logits, target):
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
@@ -782,6 +843,59 @@ class RefBackend:
         p = torch.exp(logits.to(self.dt) - lse[:, None])
         p[torch.arange(len(labels)), labels] -= 1.0
         return p * (go if go is not None else 1.0) / logits.shape[0]
+
+    @staticmethod
+    def _pix_keep(labels, K, ignore_index):
+        return (labels != ignore_index) & (labels >= 0) & (labels < K)
+
+    def pixel_ce_fwd(self, logits, labels, weight=None, ignore_index=-100):
+        x = logits.to(self.dt)
+        K = x.shape[1]
+        keep = self._pix_keep(labels, K, ignore_index)
+        lab = torch.where(keep, labels, torch.full_like(labels, ignore_index))   # out of range: ignored
+        w = weight.to(self.dt) if weight is not None else None
+        loss = F.cross_entropy(x, lab, weight=w, ignore_index=ignore_index)
+        lse = torch.logsumexp(x, 1).reshape(-1)
+        wt = w[labels.clamp(0, K - 1)] if w is not None else torch.ones_like(lse).view(labels.shape)
+        den = (wt * keep).sum().reshape(1)
+        return loss, lse, den
+
+    def pixel_ce_bwd(self, logits, labels, lse, den, go, weight=None, ignore_index=-100):
+        x = logits.to(self.dt)
+        N, K, H, W = x.shape
+        keep = self._pix_keep(labels, K, ignore_index)
+        t = labels.clamp(0, K - 1)
+        p = torch.exp(x - lse.view(N, 1, H, W))
+        p = p - F.one_hot(t, K).permute(0, 3, 1, 2).to(self.dt)
+        g = (go if go is not None else 1.0) / den
+        if weight is not None:
+            g = g * weight.to(self.dt)[t]
+        else:
+            g = g * torch.ones_like(lse).view(labels.shape)
+        d = torch.where(keep.unsqueeze(1), p * g.unsqueeze(1), torch.zeros((), dtype=self.dt, device=x.device))
+        out = torch.empty_like(logits, dtype=self.dt)
+        out.copy_(d)
+        return out
+
+    def seg_counts(self, logits, labels, ignore_index=-100):
+        N, K = logits.shape[:2]
+        keep = self._pix_keep(labels, K, ignore_index).flatten(1)
+        pred = logits.argmax(1).flatten(1)
+        t = labels.clamp(0, K - 1).flatten(1)
+        cls = torch.arange(K, device=logits.device).view(1, K, 1)
+        p = (pred.unsqueeze(1) == cls) & keep.unsqueeze(1)
+        g = (t.unsqueeze(1) == cls) & keep.unsqueeze(1)
+        return torch.stack([(p & g).sum(2), p.sum(2), g.sum(2)], 2).to(torch.int64)
+
+    def head_dgrad_bn(self, dl: Act, K, wT, ldw, dx: Act, fuse):
+        """dx[m, c] = sum_k dl[m, k] * wT[c * ldw + k], ReLU-masked by relu(BN(z)); BN-backward partials."""
+        d = dl.nhwc()[..., :K].to(self.dt)
+        w = wT.reshape(-1, ldw)[:dx.C, :K].to(self.dt)
+        zz = fuse.z.nhwc().to(self.dt)
+        keep = (zz * fuse.scale + fuse.shift) > 0
+        dx.nhwc().copy_((d @ w.t()) * keep)
+        v = dx.nhwc().to(self.dt)
+        return torch.stack([v.sum((0, 1, 2)), (v * zz).sum((0, 1, 2))]).unsqueeze(0)
 
     def bce_fwd(self, logits, target):
         return F.binary_cross_entropy_with_logits(logits.to(self.dt), target.to(self.dt))

@@ -9,7 +9,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from .backend import make_backend
+from .backend import make_backend, pixel_strides
 
 _BE = {}
 _ONES = {}
@@ -69,7 +69,55 @@ class _BCE(torch.autograd.Function):
         return g.view(logits.shape).to(logits.dtype), None
 
 
-def cross_entropy(logits, labels):
+def _pixel_layout(logits):
+    """The logits as the pixel kernels address them: unchanged in the two native layouts (contiguous
+    NCHW, or the engine's NHWC buffer viewed as NCHW), else a contiguous copy."""
+    return logits if pixel_strides(logits) is not None else logits.contiguous()
+
+
+class _PixelCE(torch.autograd.Function):
+    """Pixel-wise softmax cross-entropy: logits [N, K, H, W] (read in place, no copy), labels int64
+    [N, H, W]; the gradient comes back in the strides of the logits."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, ignore_index):
+        be = _be(logits.device, logits.dtype)
+        x = _pixel_layout(logits).to(be.dt)
+        labels = labels.contiguous()
+        w = weight.to(be.dt).contiguous() if weight is not None else None
+        loss, lse, den = be.pixel_ce_fwd(x, labels, w, ignore_index)
+        ctx.save_for_backward(x, labels, lse, den, w)
+        ctx.ignore_index = ignore_index
+        ctx.in_dtype = logits.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, go):
+        x, labels, lse, den, w = ctx.saved_tensors
+        be = _be(x.device, x.dtype)
+        g = be.pixel_ce_bwd(x, labels, lse, den, go.reshape(1).to(be.dt).contiguous(), w, ctx.ignore_index)
+        return g.to(ctx.in_dtype), None, None, None
+
+
+def _check_pixel_args(logits, labels):
+    if labels.dim() != 3 or labels.dtype != torch.int64 or labels.shape != logits.shape[:1] + logits.shape[2:]:
+        raise ValueError(f"pixel-wise logits {tuple(logits.shape)} need int64 labels [N, H, W], got "
+                         f"{labels.dtype} {tuple(labels.shape)}")
+    if not 2 <= logits.shape[1] <= 256:
+        raise ValueError(f"pixel-wise losses and counts take 2..256 classes, got {logits.shape[1]}")
+
+
+def cross_entropy(logits, labels, weight=None, ignore_index=-100):
+    """Mean softmax cross-entropy.  [N, K] logits with [N] labels: the classification loss;
+    [N, K, H, W] logits with [N, H, W] labels: the pixel-wise loss with torch's ``weight`` /
+    ``ignore_index`` semantics (labels outside [0, K) are ignored as well)."""
+    if logits.dim() == 4:
+        _check_pixel_args(logits, labels)
+        if weight is not None and weight.numel() != logits.shape[1]:
+            raise ValueError(f"weight has {weight.numel()} entries for {logits.shape[1]} classes")
+        return _PixelCE.apply(logits, labels, weight, int(ignore_index))
+    if weight is not None or ignore_index != -100:
+        raise NotImplementedError("weight / ignore_index are implemented for pixel-wise ([N, K, H, W]) logits")
     return _CE.apply(logits, labels)
 
 
@@ -78,8 +126,13 @@ def bce_with_logits(logits, target):
 
 
 class CrossEntropyLoss(nn.Module):
+    def __init__(self, weight=None, ignore_index=-100):
+        super().__init__()
+        self.register_buffer("weight", weight)
+        self.ignore_index = ignore_index
+
     def forward(self, logits, labels):
-        return cross_entropy(logits, labels)
+        return cross_entropy(logits, labels, self.weight, self.ignore_index)
 
 
 class BCEWithLogitsLoss(nn.Module):
@@ -99,3 +152,35 @@ def dice_per_sample(logits, target) -> torch.Tensor:
     (reference train.py:121-137).  logits [N,1,H,W] or [N,H,W]; target [N,H,W]."""
     lg = logits.reshape(target.shape).float().contiguous()
     return _be(logits.device, logits.dtype).dice(lg, target.float().contiguous())
+
+
+@torch.no_grad()
+def seg_counts(logits, labels, ignore_index=-100) -> torch.Tensor:
+    """int64 [N, K, 3]: per sample and class c the exact pixel counts {|pred = c and target = c|,
+    |pred = c|, |target = c|}, pred = argmax over the classes (ties to the lowest index).  Pixels whose
+    label is ``ignore_index`` or outside [0, K) count nowhere.  logits [N, K, H, W], labels int64 [N, H, W]."""
+    _check_pixel_args(logits, labels)
+    be = _be(logits.device, logits.dtype)
+    return be.seg_counts(_pixel_layout(logits.detach()).to(be.dt), labels.contiguous(), int(ignore_index))
+
+
+@torch.no_grad()
+def dice_multiclass(logits, labels, ignore_index=-100) -> torch.Tensor:
+    """Per-sample Dice [N] of argmax(logits) against integer labels: the mean over the foreground
+    classes 1..K-1 of (2 inter + 1e-8) / (pred + target + 1e-8); a class absent from both scores 1.0
+    (the reference's empty-mask rule, train.py:133-137, per class)."""
+    c = seg_counts(logits, labels, ignore_index)[:, 1:].double()
+    uni = c[..., 1] + c[..., 2]
+    d = torch.where(uni > 0, (2 * c[..., 0] + 1e-8) / (uni + 1e-8), torch.ones_like(uni))
+    return d.mean(1).float()
+
+
+@torch.no_grad()
+def mean_iou(logits, labels, ignore_index=-100) -> torch.Tensor:
+    """Mean intersection-over-union (scalar) of argmax(logits) against integer labels: the counts are
+    summed over the batch, classes whose union is empty are left out of the mean."""
+    c = seg_counts(logits, labels, ignore_index).sum(0).double()
+    union = c[:, 1] + c[:, 2] - c[:, 0]
+    has = union > 0
+    iou = torch.where(has, c[:, 0] / union.clamp_min(1), torch.zeros_like(union))
+    return (iou.sum() / has.sum()).float()
