@@ -13,6 +13,10 @@ Additions: --synthetic, --image_size, --in_channels, --data_dir, --scale, --up_s
 --backend, --device, --max_norm, --steps_per_epoch, --workers, and multi-class masks: --num_classes K > 1
 trains UNet(out_classes=K) on the integer class-index masks with the pixel-wise CrossEntropyLoss
 (--ignore_index) and evaluates the mean foreground Dice of the argmax (ops.dice_multiclass).
+--loss {ce,dice,ce+dice} (default ce: the criteria above) trains on the differentiable soft Dice as well:
+sigmoid form for --num_classes 1, softmax form for K > 1 (ops.bce_dice_loss / ce_dice_loss / dice_loss;
+--dice_weight, --dice_smooth, --dice_background 0 to leave class 0 out of the mean).  On the GPU the Dice
+sums and gradient ride in the cross-entropy kernels' passes: one forward, one finish, one backward.
 """
 from __future__ import annotations
 
@@ -31,7 +35,8 @@ from tqdm import tqdm
 from .. import parallel
 from ..data import CarvanaDataset, DeviceBatches, DeviceCachedDataset, DistributedSampler, SyntheticMasks
 from ..models import UNet
-from ..ops import BCEWithLogitsLoss, CrossEntropyLoss, backward, dice_multiclass, dice_per_sample
+from ..ops import (BCEDiceLoss, BCEWithLogitsLoss, CEDiceLoss, CrossEntropyLoss, DiceLoss, backward, dice_multiclass,
+                   dice_per_sample)
 from ..optim import Adam, clip_grad_norm_
 from ..utils.graphs import CapturedStep
 from ..utils.checkpoint import load_checkpoint, resume_state, save_checkpoint, set_rng_state
@@ -56,6 +61,13 @@ def build_argparser() -> argparse.ArgumentParser:
                         "logits per pixel, pixel-wise cross-entropy on the mask's class indices")
     p.add_argument("--ignore_index", type=int, default=-100,
                    help="label left out of the multi-class loss and Dice (--num_classes > 1)")
+    p.add_argument("--loss", default="ce", choices=["ce", "dice", "ce+dice"],
+                   help="ce: BCEWithLogits (--num_classes 1) / pixel-wise cross-entropy (K > 1); dice: the soft Dice "
+                        "loss of sigmoid / softmax; ce+dice: their sum, computed in the passes of ce alone")
+    p.add_argument("--dice_weight", type=float, default=1.0, help="weight of the Dice term (--loss ce+dice)")
+    p.add_argument("--dice_smooth", type=float, default=1.0, help="smoothing constant of the soft Dice (> 0)")
+    p.add_argument("--dice_background", type=int, default=1, choices=[0, 1],
+                   help="0: leave class 0 out of the multi-class Dice mean")
     p.add_argument("--data_dir", default="data")
     p.add_argument("--scale", type=float, default=0.2)
     p.add_argument("--up_sample_mode", default="conv_transpose", choices=["conv_transpose", "bilinear"])
@@ -198,6 +210,28 @@ def benchmark(args, train_step, captured, x, y, comm, device) -> dict:
     return {"images_per_sec": ips}
 
 
+def build_criterion(args):
+    """--loss ce (the default): today's BCEWithLogitsLoss / CrossEntropyLoss; dice, ce+dice: the fused soft
+    Dice losses, sigmoid form for --num_classes 1, softmax form (honouring --ignore_index) for K > 1."""
+    K = args.num_classes
+    kind = getattr(args, "loss", "ce")   # (callers that build the namespace themselves)
+    if kind == "ce":
+        return CrossEntropyLoss(ignore_index=args.ignore_index) if K > 1 else BCEWithLogitsLoss()
+    if kind not in ("dice", "ce+dice"):
+        raise ValueError(f"--loss must be ce, dice or ce+dice, got {kind!r}")
+    smooth = getattr(args, "dice_smooth", 1.0)
+    if kind == "dice":
+        if K > 1:
+            return DiceLoss(smooth=smooth, include_background=bool(getattr(args, "dice_background", 1)),
+                            ignore_index=args.ignore_index)
+        return DiceLoss(smooth=smooth)
+    dw = getattr(args, "dice_weight", 1.0)
+    if K > 1:
+        return CEDiceLoss(ignore_index=args.ignore_index, dice_weight=dw, smooth=smooth,
+                          include_background=bool(getattr(args, "dice_background", 1)))
+    return BCEDiceLoss(dice_weight=dw, smooth=smooth)
+
+
 def run(args) -> dict:
     if args.num_classes < 1:   # (callers that build the namespace themselves)
         raise ValueError(f"--num_classes must be >= 1, got {args.num_classes}")
@@ -221,7 +255,7 @@ def run(args) -> dict:
     ddp = parallel.DistributedDataParallel(model, bucket_cap_mb=args.bucket_mb)
     model_filepath = os.path.join(args.model_dir, args.model_filename)
     optimizer = Adam(model.parameters(), lr=args.learning_rate)
-    criterion = CrossEntropyLoss(ignore_index=args.ignore_index) if K > 1 else BCEWithLogitsLoss()
+    criterion = build_criterion(args)
     start_epoch = 0
     if args.resume:
         # weights (reference layout) + the sidecar: Adam moments and step, next epoch, RNG states

@@ -5,6 +5,7 @@
 #include "ops.h"
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "common.h"
@@ -337,6 +338,77 @@ void seg_counts(const at::Tensor& logits, int64_t sn, int64_t sk, int64_t sp, in
                          ptr<int64_t>(counts), cur_stream()),
         "seg_counts");
 }
+// Soft Dice fused into the pixel CE / BCE passes (seg_dice.hip).  The weights are checked here, host-side:
+// finite, >= 0, not both 0, smooth > 0; the partial buffers are allocated here as pixel_ce_fwd's.
+static void dice_weight_check(double a, double b, double smooth, const char* what) {
+  if (!std::isfinite(a) || !std::isfinite(b) || a < 0 || b < 0 || (a == 0 && b == 0))
+    throw std::runtime_error(std::string(what) + ": the two loss weights must be finite, >= 0 and not both 0");
+  if (!std::isfinite(smooth) || !(smooth > 0)) throw std::runtime_error(std::string(what) + ": smooth must be > 0");
+}
+void pixel_ce_dice_fwd(const at::Tensor& logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                       const at::Tensor& labels, int64_t ignore_index, const c10::optional<at::Tensor>& weight,
+                       double ce_weight, double dice_weight, double smooth, bool include_background, at::Tensor lse,
+                       at::Tensor loss, at::Tensor den, at::Tensor tab) {
+  pix_check(logits, sn, sk, sp, N, K, HW, labels, "pixel_ce_dice_fwd");
+  pix_weight_check(weight, K, "pixel_ce_dice_fwd");
+  dice_weight_check(ce_weight, dice_weight, smooth, "pixel_ce_dice_fwd");
+  f32_numel(lse, (int64_t)N * HW, "pixel_ce_dice_fwd lse");
+  f32_numel(loss, 1, "pixel_ce_dice_fwd loss");
+  f32_numel(den, 1, "pixel_ce_dice_fwd den");
+  f32_numel(tab, (int64_t)N * K * 2, "pixel_ce_dice_fwd tab");
+  const int64_t gx = dlmpi_seg_dice_blocks(HW, N);
+  at::Tensor part_ce = at::empty({N, gx, 2}, logits.options());
+  at::Tensor part_d = at::empty({N, gx, K, 3}, logits.options());
+  check(dlmpi_pixel_ce_dice_fwd(ptr<float>(logits), sn, sk, sp, N, K, HW, ptr<int64_t>(labels), ignore_index,
+                                optr<float>(weight), (float)ce_weight, (float)dice_weight, (float)smooth,
+                                include_background ? 1 : 0, ptr<float>(lse), ptr<float>(part_ce), ptr<float>(part_d),
+                                ptr<float>(loss), ptr<float>(den), ptr<float>(tab), cur_stream()),
+        "pixel_ce_dice_fwd");
+}
+void pixel_ce_dice_bwd(const at::Tensor& logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                       const at::Tensor& labels, int64_t ignore_index, const c10::optional<at::Tensor>& weight,
+                       const at::Tensor& lse, const c10::optional<at::Tensor>& go, const at::Tensor& den,
+                       const at::Tensor& tab, double ce_weight, at::Tensor dlogits) {
+  pix_check(logits, sn, sk, sp, N, K, HW, labels, "pixel_ce_dice_bwd");
+  pix_check(dlogits, sn, sk, sp, N, K, HW, labels, "pixel_ce_dice_bwd dlogits");
+  pix_weight_check(weight, K, "pixel_ce_dice_bwd");
+  if (!std::isfinite(ce_weight) || ce_weight < 0) throw std::runtime_error("pixel_ce_dice_bwd: ce_weight");
+  f32_numel(lse, (int64_t)N * HW, "pixel_ce_dice_bwd lse");
+  f32_numel(den, 1, "pixel_ce_dice_bwd den");
+  f32_numel(tab, (int64_t)N * K * 2, "pixel_ce_dice_bwd tab");
+  if (go && go->defined()) f32_numel(*go, 1, "pixel_ce_dice_bwd go");
+  check(dlmpi_pixel_ce_dice_bwd(ptr<float>(logits), sn, sk, sp, N, K, HW, ptr<int64_t>(labels), ignore_index,
+                                optr<float>(weight), ptr<float>(lse), optr<float>(go), ptr<float>(den),
+                                ptr<float>(tab), (float)ce_weight, ptr<float>(dlogits), cur_stream()),
+        "pixel_ce_dice_bwd");
+}
+// logits, target: contiguous fp32 [N][HW]
+void bce_dice_fwd(const at::Tensor& logits, const at::Tensor& target, int N, int64_t HW, double bce_weight,
+                  double dice_weight, double smooth, at::Tensor loss, at::Tensor tab) {
+  if (N < 1 || HW < 1) throw std::runtime_error("bce_dice_fwd: N, HW >= 1");
+  f32_numel(logits, (int64_t)N * HW, "bce_dice_fwd logits");
+  f32_numel(target, (int64_t)N * HW, "bce_dice_fwd target");
+  dice_weight_check(bce_weight, dice_weight, smooth, "bce_dice_fwd");
+  f32_numel(loss, 1, "bce_dice_fwd loss");
+  f32_numel(tab, (int64_t)N * 2, "bce_dice_fwd tab");
+  at::Tensor part = at::empty({N, (int64_t)dlmpi_seg_dice_blocks(HW, N), 4}, logits.options());
+  check(dlmpi_bce_dice_fwd(ptr<float>(logits), ptr<float>(target), N, HW, (float)bce_weight, (float)dice_weight,
+                           (float)smooth, ptr<float>(part), ptr<float>(loss), ptr<float>(tab), cur_stream()),
+        "bce_dice_fwd");
+}
+void bce_dice_bwd(const at::Tensor& logits, const at::Tensor& target, int N, int64_t HW,
+                  const c10::optional<at::Tensor>& go, const at::Tensor& tab, double bce_weight, at::Tensor dlogits) {
+  if (N < 1 || HW < 1) throw std::runtime_error("bce_dice_bwd: N, HW >= 1");
+  f32_numel(logits, (int64_t)N * HW, "bce_dice_bwd logits");
+  f32_numel(target, (int64_t)N * HW, "bce_dice_bwd target");
+  f32_numel(dlogits, (int64_t)N * HW, "bce_dice_bwd dlogits");
+  f32_numel(tab, (int64_t)N * 2, "bce_dice_bwd tab");
+  if (!std::isfinite(bce_weight) || bce_weight < 0) throw std::runtime_error("bce_dice_bwd: bce_weight");
+  if (go && go->defined()) f32_numel(*go, 1, "bce_dice_bwd go");
+  check(dlmpi_bce_dice_bwd(ptr<float>(logits), ptr<float>(target), N, HW, optr<float>(go), ptr<float>(tab),
+                           (float)bce_weight, ptr<float>(dlogits), cur_stream()),
+        "bce_dice_bwd");
+}
 // channels-last loss gradient x [M][K] fp32 -> y [M][Kp] activations, zero-padded
 void nhwc_pad_cast(const at::Tensor& x, int64_t M, int K, int Kp, at::Tensor y) {
   f32_numel(x, M * K, "nhwc_pad_cast x");
@@ -481,6 +553,10 @@ void register_ops(pybind11::module& m) {
   m.def("set_pixel_tiles", [](int on) { dlmpi_set_pixel_tiles(on); });
   m.def("pixel_ce_bwd", &pixel_ce_bwd);
   m.def("seg_counts", &seg_counts);
+  m.def("pixel_ce_dice_fwd", &pixel_ce_dice_fwd);
+  m.def("pixel_ce_dice_bwd", &pixel_ce_dice_bwd);
+  m.def("bce_dice_fwd", &bce_dice_fwd);
+  m.def("bce_dice_bwd", &bce_dice_bwd);
   m.def("sgd_step", &sgd_step);
   m.def("adam_step", &adam_step);
   m.def("grad_norm", &grad_norm);

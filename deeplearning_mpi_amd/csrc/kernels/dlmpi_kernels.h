@@ -421,6 +421,24 @@ hipError_t dlmpi_pixel_ce_fwd(const float* logits, int64_t sn, int64_t sk, int64
 hipError_t dlmpi_pixel_ce_bwd(const float* logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
                               const int64_t* labels, int64_t ignore_index, const float* weight, const float* lse,
                               const float* go, const float* den, float* dlogits, hipStream_t s);
+// soft Dice fused into the pixel-wise cross-entropy / BCE passes (seg_dice.hip): loss = ce_weight * CE +
+// dice_weight * (1 - mean_{n, c} (2 I + smooth) / (P + T + smooth)) over the kept pixels of each sample; a weight
+// of exactly 0 leaves its term out.  Grids are (gx, N), gx = dlmpi_seg_dice_blocks(HW, N); part_ce [N][gx][2],
+// part_d [N][gx][K][3], tab [N][K][2] = the Dice gradient's {A, B} (without go), ready after the forward call.
+int dlmpi_seg_dice_blocks(int64_t HW, int N);
+hipError_t dlmpi_pixel_ce_dice_fwd(const float* logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                                   const int64_t* labels, int64_t ignore_index, const float* weight, float ce_weight,
+                                   float dice_weight, float smooth, int include_background, float* lse,
+                                   float* part_ce, float* part_d, float* loss, float* den, float* tab, hipStream_t s);
+hipError_t dlmpi_pixel_ce_dice_bwd(const float* logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                                   const int64_t* labels, int64_t ignore_index, const float* weight, const float* lse,
+                                   const float* go, const float* den, const float* tab, float ce_weight,
+                                   float* dlogits, hipStream_t s);
+// binary form: contiguous logits / float targets [N][HW], p = sigmoid; part [N][gx][4], tab [N][2]
+hipError_t dlmpi_bce_dice_fwd(const float* logits, const float* target, int N, int64_t HW, float bce_weight,
+                              float dice_weight, float smooth, float* part, float* loss, float* tab, hipStream_t s);
+hipError_t dlmpi_bce_dice_bwd(const float* logits, const float* target, int N, int64_t HW, const float* go,
+                              const float* tab, float bce_weight, float* dlogits, hipStream_t s);
 
 // eval
 hipError_t dlmpi_argmax_correct(const float* logits, int ldl, const int64_t* labels, int N, int K, int* correct,

@@ -490,6 +490,44 @@ class NativeBackend:
         self.C.seg_counts(logits, *pixel_strides(logits), N, K, H * W, labels, int(ignore_index), out)
         return out
 
+    def pixel_ce_dice_fwd(self, logits, labels, weight=None, ignore_index=-100, ce_weight=1.0, dice_weight=1.0,
+                          smooth=1.0, include_background=True):
+        """pixel_ce_fwd with the soft Dice fused in (seg_dice.hip): loss = ce_weight * CE + dice_weight * Dice
+        -> (loss, lse [N*H*W], CE denominator, the Dice gradient's table [N, K, 2]); no host sync."""
+        N, K, H, W = logits.shape
+        dev = logits.device
+        lse = torch.empty(N * H * W, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        den = torch.empty(1, dtype=torch.float32, device=dev)
+        tab = torch.empty(N, K, 2, dtype=torch.float32, device=dev)
+        self.C.pixel_ce_dice_fwd(logits, *pixel_strides(logits), N, K, H * W, labels, int(ignore_index), weight,
+                                 float(ce_weight), float(dice_weight), float(smooth), bool(include_background), lse,
+                                 loss, den, tab)
+        return loss, lse, den, tab
+
+    def pixel_ce_dice_bwd(self, logits, labels, lse, den, tab, go, weight=None, ignore_index=-100, ce_weight=1.0):
+        """dlogits of pixel_ce_dice_fwd's loss in the strides of logits, scaled by go on the device."""
+        N, K, H, W = logits.shape
+        d = torch.empty_like(logits)   # dense input: same strides
+        assert d.stride() == logits.stride(), (d.stride(), logits.stride())
+        self.C.pixel_ce_dice_bwd(logits, *pixel_strides(logits), N, K, H * W, labels, int(ignore_index), weight, lse,
+                                 go, den, tab, float(ce_weight), d)
+        return d
+
+    def bce_dice_fwd(self, logits, target, bce_weight=1.0, dice_weight=1.0, smooth=1.0):
+        """logits, target fp32 contiguous [N, H, W] -> (bce_weight * BCE + dice_weight * Dice, table [N, 2])."""
+        N = logits.shape[0]
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        tab = torch.empty(N, 2, dtype=torch.float32, device=logits.device)
+        self.C.bce_dice_fwd(logits, target, N, logits[0].numel(), float(bce_weight), float(dice_weight),
+                            float(smooth), loss, tab)
+        return loss, tab
+
+    def bce_dice_bwd(self, logits, target, tab, go, bce_weight=1.0):
+        d = torch.empty_like(logits, memory_format=torch.contiguous_format)
+        self.C.bce_dice_bwd(logits, target, logits.shape[0], logits[0].numel(), go, tab, float(bce_weight), d)
+        return d
+
     def bce_fwd(self, logits, target):
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
         self.C.bce_fwd(logits, 1, target, logits.numel(), loss)
@@ -896,6 +934,72 @@ class RefBackend:
         dx.nhwc().copy_((d @ w.t()) * keep)
         v = dx.nhwc().to(self.dt)
         return torch.stack([v.sum((0, 1, 2)), (v * zz).sum((0, 1, 2))]).unsqueeze(0)
+
+    def _dice_terms(self, I, P, T, smooth, sel, dice_weight):
+        """Soft Dice from the per-(sample, class) sums [N, C]: (1 - mean dice over the selected classes, the
+        gradient table [N, C, 2] = {A, B} of dice_weight * that loss)."""
+        U, num = P + T + smooth, 2 * I + smooth
+        cnt = I.shape[0] * sel.sum()
+        s = dice_weight / cnt
+        tab = torch.stack([-2 * s / U * sel, s * num / (U * U) * sel], 2)
+        return 1 - (num / U * sel).sum() / cnt, tab
+
+    def pixel_ce_dice_fwd(self, logits, labels, weight=None, ignore_index=-100, ce_weight=1.0, dice_weight=1.0,
+                          smooth=1.0, include_background=True):
+        x = logits.to(self.dt)
+        N, K, H, W = x.shape
+        keep = self._pix_keep(labels, K, ignore_index).unsqueeze(1)
+        lse = torch.logsumexp(x, 1)
+        p = torch.exp(x - lse.unsqueeze(1)) * keep
+        oh = F.one_hot(labels.clamp(0, K - 1), K).permute(0, 3, 1, 2).to(self.dt) * keep
+        sel = torch.ones(K, dtype=self.dt, device=x.device)
+        if not include_background:
+            sel[0] = 0
+        dl, tab = self._dice_terms((p * oh).flatten(2).sum(2), p.flatten(2).sum(2), oh.flatten(2).sum(2), smooth, sel,
+                                   dice_weight)
+        loss = dice_weight * dl
+        den = torch.zeros(1, dtype=self.dt, device=x.device)
+        if ce_weight != 0:   # a weight of 0 leaves the term out: no NaN from an all-ignored batch
+            ce, _, den = self.pixel_ce_fwd(logits, labels, weight, ignore_index)
+            loss = loss + ce_weight * ce
+        return loss, lse.reshape(-1), den, tab
+
+    def pixel_ce_dice_bwd(self, logits, labels, lse, den, tab, go, weight=None, ignore_index=-100, ce_weight=1.0):
+        x = logits.to(self.dt)
+        N, K, H, W = x.shape
+        keep = self._pix_keep(labels, K, ignore_index).unsqueeze(1)
+        t = labels.clamp(0, K - 1)
+        p = torch.exp(x - lse.view(N, 1, H, W))
+        oh = F.one_hot(t, K).permute(0, 3, 1, 2).to(self.dt)
+        go = go if go is not None else 1.0
+        g = tab[..., 0].view(N, K, 1, 1) * oh + tab[..., 1].view(N, K, 1, 1)
+        d = p * (g - (p * g).sum(1, keepdim=True)) * go
+        if ce_weight != 0:
+            w = weight.to(self.dt)[t] if weight is not None else torch.ones_like(lse).view(labels.shape)
+            d = d + (p - oh) * (w * (ce_weight * go / den)).unsqueeze(1)
+        out = torch.empty_like(logits, dtype=self.dt)
+        out.copy_(torch.where(keep, d, torch.zeros((), dtype=self.dt, device=x.device)))
+        return out
+
+    def bce_dice_fwd(self, logits, target, bce_weight=1.0, dice_weight=1.0, smooth=1.0):
+        x, t = logits.to(self.dt).flatten(1), target.to(self.dt).flatten(1)
+        p = torch.sigmoid(x)
+        sel = torch.ones(1, dtype=self.dt, device=x.device)
+        dl, tab = self._dice_terms((p * t).sum(1, keepdim=True), p.sum(1, keepdim=True), t.sum(1, keepdim=True), smooth,
+                                   sel, dice_weight)
+        loss = dice_weight * dl
+        if bce_weight != 0:
+            loss = loss + bce_weight * F.binary_cross_entropy_with_logits(x, t)
+        return loss, tab.reshape(-1, 2)
+
+    def bce_dice_bwd(self, logits, target, tab, go, bce_weight=1.0):
+        x, t = logits.to(self.dt).flatten(1), target.to(self.dt).flatten(1)
+        p = torch.sigmoid(x)
+        go = go if go is not None else 1.0
+        d = p * (1 - p) * (tab[:, :1] * t + tab[:, 1:]) * go
+        if bce_weight != 0:
+            d = d + (p - t) * (bce_weight * go / x.numel())
+        return d.view(logits.shape)
 
     def bce_fwd(self, logits, target):
         return F.binary_cross_entropy_with_logits(logits.to(self.dt), target.to(self.dt))

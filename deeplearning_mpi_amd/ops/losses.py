@@ -3,8 +3,12 @@
 ``CrossEntropyLoss`` / ``BCEWithLogitsLoss`` are drop-in for the torch modules the reference uses
 (/root/reference/pytorch/resnet/main.py:113, /root/reference/pytorch/unet/train.py:162) for the
 ``reduction='mean'`` case: one kernel for the loss, one for the gradient, deterministic reductions.
+``ce_dice_loss`` / ``bce_dice_loss`` / ``dice_loss`` add the differentiable soft Dice of segmentation
+training, computed in the same passes over the logits as the cross-entropy / BCE alone.
 """
 from __future__ import annotations
+
+import math
 
 import torch
 import torch.nn as nn
@@ -123,6 +127,142 @@ def cross_entropy(logits, labels, weight=None, ignore_index=-100):
 
 def bce_with_logits(logits, target):
     return _BCE.apply(logits, target)
+
+
+class _PixelCEDice(torch.autograd.Function):
+    """ce_weight * pixel-wise cross-entropy + dice_weight * soft Dice in the passes of _PixelCE: one fused
+    forward, one finish, one fused backward; logits read in place, gradient in their strides."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, ignore_index, ce_weight, dice_weight, smooth, include_background):
+        be = _be(logits.device, logits.dtype)
+        x = _pixel_layout(logits).to(be.dt)
+        labels = labels.contiguous()
+        w = weight.to(be.dt).contiguous() if weight is not None else None
+        loss, lse, den, tab = be.pixel_ce_dice_fwd(x, labels, w, ignore_index, ce_weight, dice_weight, smooth,
+                                                   include_background)
+        ctx.save_for_backward(x, labels, lse, den, tab, w)
+        ctx.ignore_index, ctx.ce_weight, ctx.in_dtype = ignore_index, ce_weight, logits.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, go):
+        x, labels, lse, den, tab, w = ctx.saved_tensors
+        be = _be(x.device, x.dtype)
+        g = be.pixel_ce_dice_bwd(x, labels, lse, den, tab, go.reshape(1).to(be.dt).contiguous(), w, ctx.ignore_index,
+                                 ctx.ce_weight)
+        return (g.to(ctx.in_dtype),) + (None,) * 7
+
+
+class _BCEDice(torch.autograd.Function):
+    """bce_weight * BCE-with-logits + dice_weight * soft Dice of sigmoid(logits), per sample [N, ...]."""
+
+    @staticmethod
+    def forward(ctx, logits, target, bce_weight, dice_weight, smooth):
+        be = _be(logits.device, logits.dtype)
+        x = logits.contiguous().to(be.dt)
+        target = target.contiguous().to(be.dt)
+        loss, tab = be.bce_dice_fwd(x, target, bce_weight, dice_weight, smooth)
+        ctx.save_for_backward(x, target, tab)
+        ctx.bce_weight, ctx.in_dtype = bce_weight, logits.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, go):
+        x, target, tab = ctx.saved_tensors
+        be = _be(x.device, x.dtype)
+        g = be.bce_dice_bwd(x, target, tab, go.reshape(1).to(be.dt).contiguous(), ctx.bce_weight)
+        return g.view(x.shape).to(ctx.in_dtype), None, None, None, None
+
+
+def _check_dice_args(w0, w1, smooth, names):
+    for v, n in ((w0, names[0]), (w1, names[1])):
+        if not math.isfinite(v) or v < 0:
+            raise ValueError(f"{n} must be finite and >= 0, got {v}")
+    if w0 == 0 and w1 == 0:
+        raise ValueError(f"{names[0]} and {names[1]} must not both be 0")
+    if not (math.isfinite(smooth) and smooth > 0):
+        raise ValueError(f"smooth must be > 0 (it keeps an empty sample at dice = 1), got {smooth}")
+
+
+def ce_dice_loss(logits, labels, weight=None, ignore_index=-100, ce_weight=1.0, dice_weight=1.0, smooth=1.0,
+                 include_background=True):
+    """``ce_weight * CE + dice_weight * (1 - mean dice)`` for [N, K, H, W] logits and int64 [N, H, W] labels.
+    CE is :func:`cross_entropy` (``weight`` applies to it only); dice[n, c] = (2 I + smooth) / (P + T + smooth)
+    with I = sum p_c [y = c], P = sum p_c, T = sum [y = c] over the kept pixels of sample n (p the softmax,
+    kept as in CE), averaged over the samples and all classes (``include_background=False``: classes 1..K-1).
+    A sample without kept pixels has dice 1.  On the GPU the Dice sums and gradient ride in the CE kernels'
+    passes; ``dice_weight=0`` is :func:`cross_entropy` itself."""
+    ce_weight, dice_weight, smooth = float(ce_weight), float(dice_weight), float(smooth)
+    _check_dice_args(ce_weight, dice_weight, smooth, ("ce_weight", "dice_weight"))
+    if logits.dim() != 4:
+        raise ValueError(f"ce_dice_loss takes [N, K, H, W] logits, got {tuple(logits.shape)}")
+    _check_pixel_args(logits, labels)
+    if weight is not None and weight.numel() != logits.shape[1]:
+        raise ValueError(f"weight has {weight.numel()} entries for {logits.shape[1]} classes")
+    if dice_weight == 0:
+        loss = _PixelCE.apply(logits, labels, weight, int(ignore_index))
+        return loss if ce_weight == 1 else loss * ce_weight
+    return _PixelCEDice.apply(logits, labels, weight, int(ignore_index), ce_weight, dice_weight, smooth,
+                              bool(include_background))
+
+
+def bce_dice_loss(logits, target, bce_weight=1.0, dice_weight=1.0, smooth=1.0):
+    """``bce_weight * BCE + dice_weight * (1 - mean_n dice[n])`` for logits [N, H, W] or [N, 1, H, W] and a
+    float target [N, H, W] in [0, 1]: p = sigmoid(logits), dice[n] = (2 sum p t + smooth) / (sum p + sum t +
+    smooth).  ``dice_weight=0`` is :func:`bce_with_logits` itself."""
+    bce_weight, dice_weight, smooth = float(bce_weight), float(dice_weight), float(smooth)
+    _check_dice_args(bce_weight, dice_weight, smooth, ("bce_weight", "dice_weight"))
+    if logits.dim() == target.dim() + 1 and logits.shape[1] == 1:
+        logits = logits.squeeze(1)
+    if target.dim() < 2 or logits.shape != target.shape or not target.is_floating_point():
+        raise ValueError(f"bce_dice_loss takes logits [N, H, W] or [N, 1, H, W] and a float target [N, H, W], got "
+                         f"{tuple(logits.shape)} and {target.dtype} {tuple(target.shape)}")
+    if dice_weight == 0:
+        loss = _BCE.apply(logits, target)
+        return loss if bce_weight == 1 else loss * bce_weight
+    return _BCEDice.apply(logits, target, bce_weight, dice_weight, smooth)
+
+
+def dice_loss(logits, target, smooth=1.0, include_background=True, ignore_index=-100):
+    """The soft Dice loss alone: int64 class-index targets -> the softmax form of :func:`ce_dice_loss`
+    (``ce_weight=0``), float targets -> the sigmoid form of :func:`bce_dice_loss` (``bce_weight=0``)."""
+    if target.dtype == torch.int64:
+        return ce_dice_loss(logits, target, None, ignore_index, 0.0, 1.0, smooth, include_background)
+    if target.is_floating_point():
+        return bce_dice_loss(logits, target, 0.0, 1.0, smooth)
+    raise ValueError(f"dice_loss takes int64 class indices or a float target, got {target.dtype}")
+
+
+class CEDiceLoss(nn.Module):
+    def __init__(self, weight=None, ignore_index=-100, ce_weight=1.0, dice_weight=1.0, smooth=1.0,
+                 include_background=True):
+        super().__init__()
+        self.register_buffer("weight", weight)
+        self.ignore_index, self.ce_weight, self.dice_weight = ignore_index, ce_weight, dice_weight
+        self.smooth, self.include_background = smooth, include_background
+
+    def forward(self, logits, labels):
+        return ce_dice_loss(logits, labels, self.weight, self.ignore_index, self.ce_weight, self.dice_weight,
+                            self.smooth, self.include_background)
+
+
+class BCEDiceLoss(nn.Module):
+    def __init__(self, bce_weight=1.0, dice_weight=1.0, smooth=1.0):
+        super().__init__()
+        self.bce_weight, self.dice_weight, self.smooth = bce_weight, dice_weight, smooth
+
+    def forward(self, logits, target):
+        return bce_dice_loss(logits, target, self.bce_weight, self.dice_weight, self.smooth)
+
+
+class DiceLoss(nn.Module):
+    def __init__(self, smooth=1.0, include_background=True, ignore_index=-100):
+        super().__init__()
+        self.smooth, self.include_background, self.ignore_index = smooth, include_background, ignore_index
+
+    def forward(self, logits, target):
+        return dice_loss(logits, target, self.smooth, self.include_background, self.ignore_index)
 
 
 class CrossEntropyLoss(nn.Module):
