@@ -26,7 +26,7 @@ from .. import parallel
 from ..data import CIFAR10, CifarTransform, DeviceBatches, DeviceImageDataset, DistributedSampler, SyntheticImages
 from ..models import ARCHS
 from ..ops import CrossEntropyLoss, backward, top1_correct
-from ..optim import SGD
+from ..optim import LARS, SGD
 from ..utils.checkpoint import load_checkpoint, resume_state, save_checkpoint, set_rng_state
 from ..utils.graphs import CapturedStep
 
@@ -68,7 +68,31 @@ def build_argparser(variant: str = "main") -> argparse.ArgumentParser:
                         "(data/device.py); auto = on for GPU training on real data")
     p.add_argument("--benchmark_steps", type=int, default=0,
                    help="time this many steps on a synthetic device batch, print images/sec and exit")
+    add_layerwise_args(p, "sgd", "lars")
     return p
+
+
+def add_layerwise_args(p, plain: str, layerwise: str):
+    """--optimizer and the flags that only the layer-wise optimizer (LARS / LAMB) takes."""
+    p.add_argument("--optimizer", default=plain, choices=[plain, layerwise],
+                   help=f"{layerwise}: layer-wise trust ratios for a large global batch (no weight decay or "
+                        "adaptation for BatchNorm and bias parameters)")
+    p.add_argument("--lr_schedule", default=None, choices=["constant", "cosine", "poly"],
+                   help=f"learning-rate schedule, evaluated on the device ({layerwise} only; default constant)")
+    p.add_argument("--warmup_steps", type=int, default=None, help=f"linear warm-up updates ({layerwise} only)")
+    p.add_argument("--trust_coefficient", type=float, default=1e-3, help="trust coefficient of LARS (LAMB's ratio has none)")
+
+
+def check_layerwise_args(parser, args, plain: str):
+    if args.optimizer == plain and (args.lr_schedule is not None or args.warmup_steps is not None):
+        parser.error(f"--lr_schedule / --warmup_steps need the layer-wise optimizer, not --optimizer {plain}")
+    if args.warmup_steps is not None and args.warmup_steps < 0:
+        parser.error("--warmup_steps must be >= 0")
+
+
+def schedule_of(args, total_steps: int) -> dict:
+    return dict(kind=args.lr_schedule or "constant", warmup_steps=args.warmup_steps or 0,
+                total_steps=max(1, int(total_steps)))
 
 
 def use_graph(args, device, pixels=None, comm_backend="single") -> bool:
@@ -162,7 +186,12 @@ def run(args) -> dict:
         test_loader = DataLoader(test_set, batch_size=test_bs, shuffle=False, num_workers=args.workers,
                                  pin_memory=pin, generator=torch.Generator().manual_seed(args.random_seed))
     criterion = CrossEntropyLoss()
-    optimizer = SGD(model.parameters(), lr=args.learning_rate, momentum=0.9, weight_decay=1e-5)
+    if getattr(args, "optimizer", "sgd") == "lars":
+        steps = args.benchmark_steps or args.num_epochs * (args.steps_per_epoch or len(train_loader))
+        optimizer = LARS(model.parameters(), lr=args.learning_rate, momentum=0.9, weight_decay=1e-5,
+                         trust_coefficient=args.trust_coefficient, schedule=schedule_of(args, steps))
+    else:
+        optimizer = SGD(model.parameters(), lr=args.learning_rate, momentum=0.9, weight_decay=1e-5)
     start_epoch = 0
     if args.resume:
         # weights (reference layout) + the sidecar: optimizer state, next epoch, RNG states
@@ -263,5 +292,7 @@ def benchmark(args, train_step, captured, x, y, comm, device) -> dict:
 
 
 def main(variant="main", argv=None):
-    args = build_argparser(variant).parse_args(argv)
+    parser = build_argparser(variant)
+    args = parser.parse_args(argv)
+    check_layerwise_args(parser, args, "sgd")
     return run(args)

@@ -37,10 +37,10 @@ from ..data import CarvanaDataset, DeviceBatches, DeviceCachedDataset, Distribut
 from ..models import UNet
 from ..ops import (BCEDiceLoss, BCEWithLogitsLoss, CEDiceLoss, CrossEntropyLoss, DiceLoss, backward, dice_multiclass,
                    dice_per_sample)
-from ..optim import Adam, clip_grad_norm_
+from ..optim import LAMB, Adam, clip_grad_norm_
 from ..utils.graphs import CapturedStep
 from ..utils.checkpoint import load_checkpoint, resume_state, save_checkpoint, set_rng_state
-from .classification import use_graph
+from .classification import add_layerwise_args, check_layerwise_args, schedule_of, use_graph
 
 
 def build_argparser() -> argparse.ArgumentParser:
@@ -90,6 +90,9 @@ def build_argparser() -> argparse.ArgumentParser:
                         "eagerly); auto = on for launch-bound GPU training")
     p.add_argument("--benchmark_steps", type=int, default=0,
                    help="time this many steps on a synthetic device batch, print images/sec and exit")
+    add_layerwise_args(p, "adam", "lamb")
+    p.add_argument("--weight_decay", type=float, default=None,
+                   help="weight decay (default: 0 for adam, 0.01 for lamb)")
     return p
 
 
@@ -254,7 +257,13 @@ def run(args) -> dict:
     model.precision = args.precision
     ddp = parallel.DistributedDataParallel(model, bucket_cap_mb=args.bucket_mb)
     model_filepath = os.path.join(args.model_dir, args.model_filename)
-    optimizer = Adam(model.parameters(), lr=args.learning_rate)
+    wd = getattr(args, "weight_decay", None)
+    if getattr(args, "optimizer", "adam") == "lamb":
+        steps = args.benchmark_steps or args.num_epochs * (args.steps_per_epoch or len(train_loader))
+        optimizer = LAMB(model.parameters(), lr=args.learning_rate, weight_decay=0.01 if wd is None else wd,
+                         schedule=schedule_of(args, steps))
+    else:
+        optimizer = Adam(model.parameters(), lr=args.learning_rate, weight_decay=wd or 0.0)
     criterion = build_criterion(args)
     start_epoch = 0
     if args.resume:
@@ -349,6 +358,7 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.num_classes < 1:
         p.error(f"--num_classes must be >= 1, got {args.num_classes}")
+    check_layerwise_args(p, args, "adam")
     return args
 
 

@@ -447,6 +447,100 @@ void scale_(at::Tensor x, const at::Tensor& coef) {
   check(dlmpi_scale_f32(ptr<float>(x), x.numel(), ptr<float>(coef), cur_stream()), "scale");
 }
 
+// ---- layer-wise optimizers: segment / chunk tables of ParamArena.segments() (dlmpi_kernels.h) ----
+struct LwTables {
+  int nchunks, T;
+};
+static void i32_gpu(const at::Tensor& t, int64_t n, const char* what) {
+  if (t.scalar_type() != at::kInt || !t.is_contiguous() || t.numel() != n || !t.is_cuda())
+    throw std::runtime_error(std::string(what) + ": contiguous int32 GPU tensor of " + std::to_string(n) + " elements");
+}
+// extent = the largest start + length of the chunk table (known to the host that built it)
+static LwTables lw_tables(const at::Tensor& chunks, const at::Tensor& flags, int64_t extent, int64_t n,
+                          const char* what) {
+  if (chunks.dim() != 2 || chunks.size(1) != 4) throw std::runtime_error(std::string(what) + ": chunks must be [n][4]");
+  if (chunks.size(0) > (1 << 30)) throw std::runtime_error(std::string(what) + ": too many chunks");
+  i32_gpu(chunks, chunks.numel(), what);
+  if (flags.numel() < 1 || flags.numel() > (1 << 24)) throw std::runtime_error(std::string(what) + ": flags [T]");
+  i32_gpu(flags, flags.numel(), what);
+  if (extent < 0 || extent > n) throw std::runtime_error(std::string(what) + ": the chunk table exceeds the buffers");
+  return {(int)chunks.size(0), (int)flags.numel()};
+}
+void seg_sumsq(const at::Tensor& a, const at::Tensor& b, const at::Tensor& chunks, const at::Tensor& flags,
+               int64_t extent, at::Tensor partial) {
+  const int64_t n = a.numel();
+  const LwTables t = lw_tables(chunks, flags, extent, n, "seg_sumsq");
+  f32_numel(a, n, "seg_sumsq a");
+  f32_numel(b, n, "seg_sumsq b");
+  f32_numel(partial, 2 * (int64_t)t.nchunks, "seg_sumsq partial");
+  check(dlmpi_seg_sumsq(ptr<float>(a), ptr<float>(b), ptr<int>(chunks), t.nchunks, n, t.T, ptr<float>(partial),
+                        cur_stream()),
+        "seg_sumsq");
+}
+void seg_finish(const at::Tensor& partial, const at::Tensor& chunk_first, const at::Tensor& flags, at::Tensor tab,
+                at::Tensor step, const c10::optional<at::Tensor>& skip, int mode, double tc, double wd, double eps,
+                double b1, double b2, int kind, double base_lr, double warmup, double total, double min_lr,
+                double power) {
+  const int64_t T = flags.numel();
+  if (T < 1 || T > (1 << 24) || partial.numel() % 2) throw std::runtime_error("seg_finish: table sizes");
+  const int64_t nchunks = partial.numel() / 2;
+  f32_numel(partial, 2 * nchunks, "seg_finish partial");
+  i32_gpu(chunk_first, T + 1, "seg_finish chunk_first");
+  i32_gpu(flags, T, "seg_finish flags");
+  f32_numel(tab, dlmpi_lw_tab() + T, "seg_finish tab");
+  f32_numel(step, 1, "seg_finish step");
+  if (skip && skip->defined()) f32_numel(*skip, 1, "seg_finish skip");
+  if (mode < 0 || mode > 2 || kind < 0 || kind > 2) throw std::runtime_error("seg_finish: mode / kind");
+  check(dlmpi_seg_finish(ptr<float>(partial), (int)nchunks, ptr<int>(chunk_first), ptr<int>(flags), (int)T,
+                         ptr<float>(tab), ptr<float>(step), optr<float>(skip), mode, (float)tc, (float)wd, (float)eps,
+                         b1, b2, kind, (float)base_lr, (float)warmup, (float)total, (float)min_lr,
+                         (float)power, cur_stream()),
+        "seg_finish");
+}
+void lars_update(at::Tensor p, const at::Tensor& g, at::Tensor m, const at::Tensor& chunks, const at::Tensor& flags,
+                 int64_t extent, const at::Tensor& tab, double momentum, double wd, bool nesterov) {
+  const int64_t n = p.numel();
+  const LwTables t = lw_tables(chunks, flags, extent, n, "lars_update");
+  f32_numel(p, n, "lars_update p");
+  f32_numel(g, n, "lars_update g");
+  f32_numel(m, n, "lars_update m");
+  f32_numel(tab, dlmpi_lw_tab() + t.T, "lars_update tab");
+  check(dlmpi_lars_update(ptr<float>(p), ptr<float>(g), ptr<float>(m), ptr<int>(chunks), t.nchunks, n, ptr<int>(flags),
+                          t.T, ptr<float>(tab), (float)momentum, (float)wd, nesterov ? 1 : 0, cur_stream()),
+        "lars_update");
+}
+void lamb_moments(const at::Tensor& p, const at::Tensor& g, at::Tensor m, at::Tensor v, const at::Tensor& chunks,
+                  const at::Tensor& flags, int64_t extent, at::Tensor partial, const at::Tensor& tab,
+                  const c10::optional<at::Tensor>& clip, double b1, double b2, double eps, double wd) {
+  const int64_t n = p.numel();
+  const LwTables t = lw_tables(chunks, flags, extent, n, "lamb_moments");
+  f32_numel(p, n, "lamb_moments p");
+  f32_numel(g, n, "lamb_moments g");
+  f32_numel(m, n, "lamb_moments m");
+  f32_numel(v, n, "lamb_moments v");
+  f32_numel(partial, 2 * (int64_t)t.nchunks, "lamb_moments partial");
+  f32_numel(tab, dlmpi_lw_tab() + t.T, "lamb_moments tab");
+  if (clip && clip->defined()) f32_numel(*clip, 2, "lamb_moments clip");
+  if (!(eps > 0)) throw std::runtime_error("lamb_moments: eps > 0");
+  check(dlmpi_lamb_moments(ptr<float>(p), ptr<float>(g), ptr<float>(m), ptr<float>(v), ptr<int>(chunks), t.nchunks, n,
+                           ptr<int>(flags), t.T, ptr<float>(partial), ptr<float>(tab), optr<float>(clip), b1, b2,
+                           (float)eps, (float)wd, cur_stream()),
+        "lamb_moments");
+}
+void lamb_update(at::Tensor p, const at::Tensor& m, const at::Tensor& v, const at::Tensor& chunks,
+                 const at::Tensor& flags, int64_t extent, const at::Tensor& tab, double eps, double wd) {
+  const int64_t n = p.numel();
+  const LwTables t = lw_tables(chunks, flags, extent, n, "lamb_update");
+  f32_numel(p, n, "lamb_update p");
+  f32_numel(m, n, "lamb_update m");
+  f32_numel(v, n, "lamb_update v");
+  f32_numel(tab, dlmpi_lw_tab() + t.T, "lamb_update tab");
+  if (!(eps > 0)) throw std::runtime_error("lamb_update: eps > 0");
+  check(dlmpi_lamb_update(ptr<float>(p), ptr<float>(m), ptr<float>(v), ptr<int>(chunks), t.nchunks, n, ptr<int>(flags),
+                          t.T, ptr<float>(tab), (float)eps, (float)wd, cur_stream()),
+        "lamb_update");
+}
+
 // --------------------------------- utilities -----------------------------------------------
 void fill_(at::Tensor t, double v) {
   if (t.scalar_type() != at::kFloat || !t.is_contiguous()) throw std::runtime_error("fill_: contiguous fp32 tensor");
@@ -560,6 +654,13 @@ void register_ops(pybind11::module& m) {
   m.def("sgd_step", &sgd_step);
   m.def("adam_step", &adam_step);
   m.def("grad_norm", &grad_norm);
+  m.def("seg_sumsq", &seg_sumsq);
+  m.def("seg_finish", &seg_finish);
+  m.def("lars_update", &lars_update);
+  m.def("lamb_moments", &lamb_moments);
+  m.def("lamb_update", &lamb_update);
+  m.def("lw_chunk", []() { return dlmpi_lw_chunk(); });
+  m.def("lw_tab", []() { return dlmpi_lw_tab(); });
   m.def("scale_", &scale_);
   m.def("fill_", &fill_);
   m.def("clock_stamp", &clock_stamp);

@@ -461,6 +461,31 @@ hipError_t dlmpi_clip_coef(const float* partial, int nblk, float max_norm, float
                            hipStream_t s);
 hipError_t dlmpi_scale_f32(float* x, int64_t n, const float* coef, hipStream_t s);
 
+// layer-wise optimizers (optim_layerwise.hip).  chunks: int32 [nchunks][4] = {segment, length, start lo,
+// start hi}, length <= dlmpi_lw_chunk(), start relative to the buffers (n elements each); partial: fp32
+// [2][nchunks]; chunk_first: int32 [T + 1]; flags: int32 [T] (bit 0 no decay, bit 1 no adaptation);
+// tab: fp32 [dlmpi_lw_tab() + T] = {lr, bc1, bc2, skip, grad norm, first, next bc1, next bc2, ratio[T]};
+// step: fp32 [1], the updates applied so far, advanced by seg_finish unless the update is skipped
+int dlmpi_lw_chunk(void);
+int dlmpi_lw_tab(void);
+hipError_t dlmpi_seg_sumsq(const float* a, const float* b, const int* chunks, int nchunks, int64_t n, int T,
+                           float* partial, hipStream_t s);
+// mode 0 LARS (partials w^2, g^2; skip also when the gradient norm is not finite), 1 LAMB (w^2, u^2),
+// 2: only write the next update's bias corrections from the step count (before LAMB's first launch);
+// kind 0 constant, 1 cosine, 2 polynomial, each after `warmup` linear warm-up updates
+hipError_t dlmpi_seg_finish(const float* partial, int nchunks, const int* chunk_first, const int* flags, int T,
+                            float* tab, float* step, const float* skip, int mode, float tc, float wd, float eps,
+                            double b1, double b2, int kind, float base_lr, float warmup, float total, float min_lr,
+                            float power, hipStream_t s);   // (betas as doubles: 1 - beta^t is formed in fp64)
+hipError_t dlmpi_lars_update(float* p, const float* g, float* m, const int* chunks, int nchunks, int64_t n,
+                             const int* flags, int T, const float* tab, float momentum, float wd, int nesterov,
+                             hipStream_t s);
+hipError_t dlmpi_lamb_moments(const float* p, const float* g, float* m, float* v, const int* chunks, int nchunks,
+                              int64_t n, const int* flags, int T, float* partial, const float* tab,
+                              const float* clip, double b1, double b2, float eps, float wd, hipStream_t s);
+hipError_t dlmpi_lamb_update(float* p, const float* m, const float* v, const int* chunks, int nchunks, int64_t n,
+                             const int* flags, int T, const float* tab, float eps, float wd, hipStream_t s);
+
 // device-resident input pipeline: out[b] = normalize(augment(data[idx[b]])), [B][C][H][W] fp32 (C <= 3)
 hipError_t dlmpi_image_batch(const uint8_t* data, const int64_t* labels, const int64_t* idx, int B, int H, int W,
                              int C, int pad, int augment, uint32_t seed, uint32_t epoch, const float* mean3,

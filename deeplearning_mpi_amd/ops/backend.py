@@ -562,6 +562,29 @@ class NativeBackend:
     def scale_(self, x, coef):
         self.C.scale_(x, coef)
 
+    # layer-wise optimizers (csrc/kernels/optim_layerwise.hip): two chunk-indexed passes over the flat
+    # buffers with seg_finish between them.  plan: the optimizer's tables for these buffers
+    # (seg = Segments, flags, tab, partial); step: device count of the updates applied so far
+    def lars(self, p, g, m, plan, step, skip_flag, lr, momentum, wd, nesterov, tc, eps, sched):
+        s = plan.seg
+        kind, warm, total, min_lr, power = sched
+        self.C.seg_sumsq(p, g, s.chunks, plan.flags, s.extent, plan.partial)
+        self.C.seg_finish(plan.partial, s.chunk_first, plan.flags, plan.tab, step, skip_flag, 0, tc, wd, eps, 0.0, 0.0,
+                          kind, lr, warm, total, min_lr, power)
+        self.C.lars_update(p, g, m, s.chunks, plan.flags, s.extent, plan.tab, momentum, wd, bool(nesterov))
+
+    def lamb(self, p, g, m, v, plan, step, clip, lr, b1, b2, eps, wd, sched):
+        s = plan.seg
+        kind, warm, total, min_lr, power = sched
+        if not plan.primed:   # new tables (first step, loaded state): the bias corrections of the next update
+            self.C.seg_finish(plan.partial, s.chunk_first, plan.flags, plan.tab, step, None, 2, 0.0, wd, eps, b1, b2,
+                              kind, lr, warm, total, min_lr, power)
+            plan.primed = True
+        self.C.lamb_moments(p, g, m, v, s.chunks, plan.flags, s.extent, plan.partial, plan.tab, clip, b1, b2, eps, wd)
+        self.C.seg_finish(plan.partial, s.chunk_first, plan.flags, plan.tab, step, None if clip is None else clip[1:2],
+                          1, 0.0, wd, eps, b1, b2, kind, lr, warm, total, min_lr, power)
+        self.C.lamb_update(p, m, v, s.chunks, plan.flags, s.extent, plan.tab, eps, wd)
+
     # ---------------- utilities (per-step glue on our own kernels) ----------------
     def fill_(self, t, v):
         self.C.fill_(t, float(v))
@@ -1064,6 +1087,73 @@ class RefBackend:
     def scale_(self, x, coef):
         x.mul_(coef[0])
 
+    # layer-wise optimizers: a per-tensor loop in the backend's dtype over the same tables (the host lists
+    # of plan.seg), writing the same table: tab = [lr, bc1, bc2, skip, grad norm, first, next bc1, next bc2, ratio[T]]
+    def lars(self, p, g, m, plan, step, skip_flag, lr, momentum, wd, nesterov, tc, eps, sched):
+        s, tab = plan.seg, plan.tab
+        views = [(i, slice(o, o + n)) for i, (o, n) in enumerate(zip(s.offsets, s.numels))]
+        gn = sum((g[sl].double().pow(2).sum() for _, sl in views), torch.zeros((), dtype=torch.float64,
+                                                                               device=g.device)).sqrt()
+        tab[4] = gn
+        if (skip_flag is not None and float(skip_flag.reshape(-1)[0]) != 0) or not bool(torch.isfinite(gn)):
+            tab[3] = 1.0
+            return
+        done = float(step.reshape(-1)[0])
+        lr_t = layerwise_lr(lr, done, sched)
+        first = done == 0
+        for i, sl in views:
+            w, gi = p[sl], g[sl]
+            fl = plan.flag_words[i]
+            wdi = 0.0 if fl & 1 else wd
+            r = 1.0
+            if not fl & 2:
+                wn, gnorm = w.pow(2).sum().sqrt(), gi.pow(2).sum().sqrt()
+                if float(wn) > 0 and float(gnorm) > 0:
+                    r = tc * wn / (gnorm + wdi * wn + eps)
+            d = (gi + wdi * w) * r
+            if momentum != 0:
+                mi = m[sl]
+                if first:
+                    mi.copy_(d)
+                else:
+                    mi.mul_(momentum).add_(d)
+                d = d + momentum * mi if nesterov else mi
+            w.add_(d, alpha=-lr_t)
+            tab[8 + i] = r
+        tab[0], tab[3], tab[5] = lr_t, 0.0, float(first)
+        step.add_(1)
+
+    def lamb(self, p, g, m, v, plan, step, clip, lr, b1, b2, eps, wd, sched):
+        s, tab = plan.seg, plan.tab
+        coef = 1.0
+        if clip is not None:
+            if float(clip[1]) != 0:
+                tab[3] = 1.0
+                return
+            coef = clip[0].to(g.dtype)
+        done = float(step.reshape(-1)[0])
+        lr_t = layerwise_lr(lr, done, sched)
+        bc1, bc2 = 1 - b1 ** (done + 1), 1 - b2 ** (done + 1)
+        for i, (o, n) in enumerate(zip(s.offsets, s.numels)):
+            sl = slice(o, o + n)
+            w, gi, mi, vi = p[sl], g[sl] * coef, m[sl], v[sl]
+            fl = plan.flag_words[i]
+            mi.lerp_(gi, 1 - b1)
+            vi.mul_(b2).addcmul_(gi, gi, value=1 - b2)
+            u = (mi / bc1) / (vi.sqrt() / (bc2 ** 0.5) + eps)
+            if wd != 0 and not fl & 1:
+                u = u + wd * w
+            r = 1.0
+            if not fl & 2:
+                wn, un = w.pow(2).sum().sqrt(), u.pow(2).sum().sqrt()
+                if float(wn) > 0 and float(un) > 0:
+                    r = wn / un
+            w.sub_(u * (lr_t * r))
+            tab[8 + i] = r
+        tab[0], tab[1], tab[2], tab[3], tab[5] = lr_t, bc1, bc2, 0.0, float(done == 0)
+        tab[6], tab[7] = 1 - b1 ** (done + 2), 1 - b2 ** (done + 2)   # the next update's
+        step.add_(1)
+
     def fill_(self, t, v):
         t.fill_(v)
 
@@ -1077,6 +1167,22 @@ class RefBackend:
             d.add_(v)
         else:
             d.copy_(v)
+
+
+def layerwise_lr(base, done, sched):
+    """The learning rate of update number ``done`` + 1 (``done`` updates applied so far) under
+    sched = (kind, warmup_steps, total_steps, min_lr, power); kind 0 constant, 1 cosine, 2
+    polynomial.  seg_finish_kernel computes the same on the device."""
+    import math
+
+    kind, warm, total, min_lr, power = sched
+    if done < warm:
+        return base * (done + 1) / warm
+    if kind == 0:
+        return base
+    q = min(1.0, (done - warm) / max(1.0, total - warm))
+    f = 0.5 * (1 + math.cos(math.pi * q)) if kind == 1 else (1 - q) ** power
+    return min_lr + (base - min_lr) * f
 
 
 def make_backend(device, dtype=torch.float32, precision: str = "bf16") -> "NativeBackend | RefBackend":

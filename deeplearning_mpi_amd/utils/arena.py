@@ -39,6 +39,46 @@ def arena_of(param) -> "ParamArena | None":
     return None
 
 
+LW_CHUNK = 4096   # elements per chunk of the layer-wise optimizer kernels (csrc/kernels/optim_layerwise.hip)
+
+
+class Segments:
+    """Per-tensor tables over a flat buffer for the layer-wise optimizers (LARS / LAMB).
+
+    Host side: ``offsets`` / ``numels`` / ``flag_words`` (lists, one entry per tensor, in flat
+    order), ``order`` (for an arena: the index into ``arena.params`` of each entry), ``extent``
+    (the largest offset + numel).  Device side: ``offset`` / ``numel`` (int64 [T]), ``flags``
+    (int32 [T]; bit 0: the tensor has at most one dimension), ``chunks`` (int32 [n][4] =
+    segment, length, start low word, start high word) and ``chunk_first`` (int32 [T + 1], the
+    first chunk of each tensor).  A tensor is cut from its own start into chunks of ``chunk``
+    elements, so the chunking of a tensor does not depend on where it sits in the buffer."""
+
+    def __init__(self, offsets, numels, flag_words, device, chunk=LW_CHUNK, order=None):
+        self.offsets, self.numels, self.flag_words = list(offsets), list(numels), list(flag_words)
+        self.order = list(order) if order is not None else list(range(len(self.offsets)))
+        self.chunk = int(chunk)
+        self.extent = max([o + n for o, n in zip(self.offsets, self.numels)] + [0])
+        seg, length, start, first = [], [], [], [0]
+        for s, (o, n) in enumerate(zip(self.offsets, self.numels)):
+            for a in range(0, n, self.chunk):
+                seg.append(s)
+                length.append(min(self.chunk, n - a))
+                start.append(o + a)
+            first.append(len(seg))
+        self.nchunks = len(seg)
+        st = torch.tensor(start, dtype=torch.int64)
+        lo = st & 0xFFFFFFFF
+        lo = torch.where(lo >= 2 ** 31, lo - 2 ** 32, lo)   # the low word as a (wrapped) int32
+        table = torch.stack([torch.tensor(seg, dtype=torch.int64), torch.tensor(length, dtype=torch.int64), lo,
+                             st >> 32], 1) if seg else torch.zeros(0, 4, dtype=torch.int64)
+        dev = torch.device(device)
+        self.chunks = table.to(torch.int32).contiguous().to(dev)
+        self.chunk_first = torch.tensor(first, dtype=torch.int32).to(dev)
+        self.offset = torch.tensor(self.offsets, dtype=torch.int64).to(dev)
+        self.numel = torch.tensor(self.numels, dtype=torch.int64).to(dev)
+        self.flags = torch.tensor(self.flag_words, dtype=torch.int32).to(dev)
+
+
 def _conv_like(m):
     return isinstance(m, (nn.Conv2d, nn.ConvTranspose2d))
 
@@ -179,6 +219,21 @@ class ParamArena:
     def grad_flat(self, p) -> torch.Tensor:
         i = self.index[id(p)]
         return self.grad[self.offsets[i]:self.offsets[i] + p.numel()]
+
+    def segments(self, chunk=LW_CHUNK) -> Segments:
+        """The parameters as segments of the flat buffers, in flat order, with their chunk list
+        (cached; the first call copies the tables to the device, so make it outside a hipGraph
+        capture -- the optimizers' first eager step does).  What the kernels rely on: every tensor
+        starts on a 64-byte boundary, the padding between tensors is zero and is never written, and
+        a conv weight, though stored permuted, fills [offset, offset + numel) contiguously (norms
+        do not care about the permutation)."""
+        s = getattr(self, "_segments", None)
+        if s is None or s.chunk != chunk:
+            order = self.order
+            s = self._segments = Segments([self.offsets[i] for i in order], [self.params[i].numel() for i in order],
+                                          [1 if self.params[i].dim() <= 1 else 0 for i in order], self.device,
+                                          chunk, order=order)
+        return s
 
     def attach_grads(self):
         """Re-attach .grad views (a foreign optimizer's zero_grad(set_to_none=True) drops them)."""
