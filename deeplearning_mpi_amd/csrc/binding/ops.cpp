@@ -275,7 +275,7 @@ void dice(const at::Tensor& logits, int ldl, const at::Tensor& target, int N, in
   check(dlmpi_dice(ptr<float>(logits), ldl, ptr<float>(target), N, HW, ptr<float>(out), cur_stream()), "dice");
 }
 
-// Pixel-wise losses / counts (pixel_ce.hip): t is addressed as n*sn + k*sk + p*sp over N x K x HW; every
+// Pixel-wise losses / counts (pixel_ce.hip, seg_dice.hip): t is addressed as n*sn + k*sk + p*sp over N x K x HW; every
 // address must lie inside its storage, the labels are int64 [N*HW].
 static void pix_check(const at::Tensor& t, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
                       const at::Tensor& labels, const char* what) {
@@ -289,24 +289,37 @@ static void pix_check(const at::Tensor& t, int64_t sn, int64_t sk, int64_t sp, i
       !labels.is_cuda())
     throw std::runtime_error(std::string(what) + ": labels must be contiguous int64 [N*HW] on the GPU");
 }
-static void pix_weight_check(const c10::optional<at::Tensor>& weight, int K, const char* what) {
-  if (weight && weight->defined() &&
-      (weight->scalar_type() != at::kFloat || !weight->is_contiguous() || weight->numel() != K || !weight->is_cuda()))
-    throw std::runtime_error(std::string(what) + ": weight must be contiguous fp32 [K] on the GPU");
-}
 static void f32_numel(const at::Tensor& t, int64_t n, const char* what) {
   if (t.scalar_type() != at::kFloat || !t.is_contiguous() || t.numel() != n || !t.is_cuda())
     throw std::runtime_error(std::string(what) + ": contiguous fp32 GPU tensor of " + std::to_string(n) + " elements");
+}
+// The preambles of the four pixel-loss binders (fn: the binder's name, kept in the error texts).  tab: the fused
+// loss's Dice table [N][K][2], null for the cross-entropy alone; loss: null when the backward's preamble calls.
+static void pix_fwd_check(const std::string& fn, const at::Tensor& logits, int64_t sn, int64_t sk, int64_t sp, int N,
+                          int K, int64_t HW, const at::Tensor& labels, const c10::optional<at::Tensor>& weight,
+                          const at::Tensor& lse, const at::Tensor& den, const at::Tensor* tab, const at::Tensor* loss) {
+  pix_check(logits, sn, sk, sp, N, K, HW, labels, fn.c_str());
+  if (weight && weight->defined() &&
+      (weight->scalar_type() != at::kFloat || !weight->is_contiguous() || weight->numel() != K || !weight->is_cuda()))
+    throw std::runtime_error(fn + ": weight must be contiguous fp32 [K] on the GPU");
+  f32_numel(lse, (int64_t)N * HW, (fn + " lse").c_str());
+  f32_numel(den, 1, (fn + " den").c_str());
+  if (tab) f32_numel(*tab, (int64_t)N * K * 2, (fn + " tab").c_str());
+  if (loss) f32_numel(*loss, 1, (fn + " loss").c_str());
+}
+static void pix_bwd_check(const std::string& fn, const at::Tensor& logits, int64_t sn, int64_t sk, int64_t sp, int N,
+                          int K, int64_t HW, const at::Tensor& labels, const c10::optional<at::Tensor>& weight,
+                          const at::Tensor& lse, const at::Tensor& den, const at::Tensor* tab,
+                          const at::Tensor& dlogits, const c10::optional<at::Tensor>& go) {
+  pix_fwd_check(fn, logits, sn, sk, sp, N, K, HW, labels, weight, lse, den, tab, nullptr);
+  pix_check(dlogits, sn, sk, sp, N, K, HW, labels, (fn + " dlogits").c_str());
+  if (go && go->defined()) f32_numel(*go, 1, (fn + " go").c_str());
 }
 
 void pixel_ce_fwd(const at::Tensor& logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
                   const at::Tensor& labels, int64_t ignore_index, const c10::optional<at::Tensor>& weight,
                   at::Tensor lse, at::Tensor loss, at::Tensor den) {
-  pix_check(logits, sn, sk, sp, N, K, HW, labels, "pixel_ce_fwd");
-  pix_weight_check(weight, K, "pixel_ce_fwd");
-  f32_numel(lse, (int64_t)N * HW, "pixel_ce_fwd lse");
-  f32_numel(loss, 1, "pixel_ce_fwd loss");
-  f32_numel(den, 1, "pixel_ce_fwd den");
+  pix_fwd_check("pixel_ce_fwd", logits, sn, sk, sp, N, K, HW, labels, weight, lse, den, nullptr, &loss);
   at::Tensor partial = at::empty({dlmpi_pixel_ce_blocks((int64_t)N * HW), 2}, logits.options());
   check(dlmpi_pixel_ce_fwd(ptr<float>(logits), sn, sk, sp, N, K, HW, ptr<int64_t>(labels), ignore_index,
                            optr<float>(weight), ptr<float>(lse), ptr<float>(partial), ptr<float>(loss),
@@ -317,12 +330,7 @@ void pixel_ce_bwd(const at::Tensor& logits, int64_t sn, int64_t sk, int64_t sp, 
                   const at::Tensor& labels, int64_t ignore_index, const c10::optional<at::Tensor>& weight,
                   const at::Tensor& lse, const c10::optional<at::Tensor>& go, const at::Tensor& den,
                   at::Tensor dlogits) {
-  pix_check(logits, sn, sk, sp, N, K, HW, labels, "pixel_ce_bwd");
-  pix_check(dlogits, sn, sk, sp, N, K, HW, labels, "pixel_ce_bwd dlogits");
-  pix_weight_check(weight, K, "pixel_ce_bwd");
-  f32_numel(lse, (int64_t)N * HW, "pixel_ce_bwd lse");
-  f32_numel(den, 1, "pixel_ce_bwd den");
-  if (go && go->defined()) f32_numel(*go, 1, "pixel_ce_bwd go");
+  pix_bwd_check("pixel_ce_bwd", logits, sn, sk, sp, N, K, HW, labels, weight, lse, den, nullptr, dlogits, go);
   check(dlmpi_pixel_ce_bwd(ptr<float>(logits), sn, sk, sp, N, K, HW, ptr<int64_t>(labels), ignore_index,
                            optr<float>(weight), ptr<float>(lse), optr<float>(go), ptr<float>(den),
                            ptr<float>(dlogits), cur_stream()),
@@ -349,13 +357,8 @@ void pixel_ce_dice_fwd(const at::Tensor& logits, int64_t sn, int64_t sk, int64_t
                        const at::Tensor& labels, int64_t ignore_index, const c10::optional<at::Tensor>& weight,
                        double ce_weight, double dice_weight, double smooth, bool include_background, at::Tensor lse,
                        at::Tensor loss, at::Tensor den, at::Tensor tab) {
-  pix_check(logits, sn, sk, sp, N, K, HW, labels, "pixel_ce_dice_fwd");
-  pix_weight_check(weight, K, "pixel_ce_dice_fwd");
+  pix_fwd_check("pixel_ce_dice_fwd", logits, sn, sk, sp, N, K, HW, labels, weight, lse, den, &tab, &loss);
   dice_weight_check(ce_weight, dice_weight, smooth, "pixel_ce_dice_fwd");
-  f32_numel(lse, (int64_t)N * HW, "pixel_ce_dice_fwd lse");
-  f32_numel(loss, 1, "pixel_ce_dice_fwd loss");
-  f32_numel(den, 1, "pixel_ce_dice_fwd den");
-  f32_numel(tab, (int64_t)N * K * 2, "pixel_ce_dice_fwd tab");
   const int64_t gx = dlmpi_seg_dice_blocks(HW, N);
   at::Tensor part_ce = at::empty({N, gx, 2}, logits.options());
   at::Tensor part_d = at::empty({N, gx, K, 3}, logits.options());
@@ -369,14 +372,8 @@ void pixel_ce_dice_bwd(const at::Tensor& logits, int64_t sn, int64_t sk, int64_t
                        const at::Tensor& labels, int64_t ignore_index, const c10::optional<at::Tensor>& weight,
                        const at::Tensor& lse, const c10::optional<at::Tensor>& go, const at::Tensor& den,
                        const at::Tensor& tab, double ce_weight, at::Tensor dlogits) {
-  pix_check(logits, sn, sk, sp, N, K, HW, labels, "pixel_ce_dice_bwd");
-  pix_check(dlogits, sn, sk, sp, N, K, HW, labels, "pixel_ce_dice_bwd dlogits");
-  pix_weight_check(weight, K, "pixel_ce_dice_bwd");
+  pix_bwd_check("pixel_ce_dice_bwd", logits, sn, sk, sp, N, K, HW, labels, weight, lse, den, &tab, dlogits, go);
   if (!std::isfinite(ce_weight) || ce_weight < 0) throw std::runtime_error("pixel_ce_dice_bwd: ce_weight");
-  f32_numel(lse, (int64_t)N * HW, "pixel_ce_dice_bwd lse");
-  f32_numel(den, 1, "pixel_ce_dice_bwd den");
-  f32_numel(tab, (int64_t)N * K * 2, "pixel_ce_dice_bwd tab");
-  if (go && go->defined()) f32_numel(*go, 1, "pixel_ce_dice_bwd go");
   check(dlmpi_pixel_ce_dice_bwd(ptr<float>(logits), sn, sk, sp, N, K, HW, ptr<int64_t>(labels), ignore_index,
                                 optr<float>(weight), ptr<float>(lse), optr<float>(go), ptr<float>(den),
                                 ptr<float>(tab), (float)ce_weight, ptr<float>(dlogits), cur_stream()),

@@ -409,11 +409,12 @@ hipError_t dlmpi_bce_fwd(const float* logits, int ldl, const float* target, int6
 hipError_t dlmpi_bce_bwd(const float* logits, int ldl, const float* target, int64_t M, const float* go, float scale,
                          float* dlogits, hipStream_t s);
 hipError_t dlmpi_sum_f32(const float* x, int64_t n, float* out, float scale, hipStream_t s);
-// pixel-wise softmax cross-entropy over N x HW pixels and K = 2..256 classes (pixel_ce.hip): logits fp32 at
-// n*sn + k*sk + p*sp (elements), labels int64 [N*HW] (ignore_index or outside [0, K): ignored), weight
+// pixel-wise softmax cross-entropy over N x HW pixels and K = 2..256 classes (pixel_ce.hip; what it
+// shares with seg_dice.hip is in pixel_softmax.h): logits fp32 at n*sn + k*sk + p*sp (elements), labels int64 [N*HW] (ignore_index or outside [0, K): ignored), weight
 // fp32 [K] or null; lse [N*HW], partial [dlmpi_pixel_ce_blocks(N*HW)][2], loss = sum w nll / sum w, den = sum w
 int dlmpi_pixel_ce_blocks(int64_t M);
-void dlmpi_set_pixel_tiles(int on);   // 0: no LDS-tile kernels for class-last logits with K > 4 (A/B)
+// 0: no LDS-tile kernels for class-last logits with K > 4, in pixel_ce.hip and seg_dice.hip alike (A/B; default 1)
+void dlmpi_set_pixel_tiles(int on);
 hipError_t dlmpi_pixel_ce_fwd(const float* logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
                               const int64_t* labels, int64_t ignore_index, const float* weight, float* lse,
                               float* partial, float* loss, float* den, hipStream_t s);
@@ -421,7 +422,7 @@ hipError_t dlmpi_pixel_ce_fwd(const float* logits, int64_t sn, int64_t sk, int64
 hipError_t dlmpi_pixel_ce_bwd(const float* logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
                               const int64_t* labels, int64_t ignore_index, const float* weight, const float* lse,
                               const float* go, const float* den, float* dlogits, hipStream_t s);
-// soft Dice fused into the pixel-wise cross-entropy / BCE passes (seg_dice.hip): loss = ce_weight * CE +
+// soft Dice fused into the pixel-wise CE / BCE passes (seg_dice.hip, pixel_softmax.h): loss = ce_weight * CE +
 // dice_weight * (1 - mean_{n, c} (2 I + smooth) / (P + T + smooth)) over the kept pixels of each sample; a weight
 // of exactly 0 leaves its term out.  Grids are (gx, N), gx = dlmpi_seg_dice_blocks(HW, N); part_ce [N][gx][2],
 // part_d [N][gx][K][3], tab [N][K][2] = the Dice gradient's {A, B} (without go), ready after the forward call.

@@ -10,48 +10,13 @@
 // per-class weight w the loss is sum w[t] nll / sum w[t] over the kept pixels (torch semantics;
 // all pixels ignored -> 0 / 0 = NaN, gradient exactly zero).
 // Reductions are two-stage with a fixed order, no float atomics: the same bits on every run.
-#include "common.h"
+// The softmax arithmetic, the addressing, the block reduction and the tile copy are pixel_softmax.h's,
+// shared with the fused CE + Dice kernels of seg_dice.hip.
+#include "pixel_softmax.h"
 
 namespace dlmpi {
 
-struct PixStrides {
-  int64_t sn, sk, sp;   // element strides of sample, class, flat pixel (h * W + w)
-};
-
 constexpr int kPixBlocksMax = 2048;
-
-__device__ __forceinline__ bool pix_kept(int64_t lab, int K, int64_t ignore_index) {
-  return lab != ignore_index && lab >= 0 && lab < K;
-}
-
-// KC > 0: K known at compile time, the pixel's logits are held in registers (one pass, one load each;
-// VEC: class stride 1 and an aligned base, so they are one 8 / 16 byte load).  KC == 0: any K, online
-// softmax (running maximum and rescaled sum) in one pass.
-template <int KC, bool VEC>
-__device__ __forceinline__ void pix_load(const float* __restrict__ p, int64_t sk, float* v) {
-  if constexpr (VEC && KC == 2) {
-    const float2 t = *reinterpret_cast<const float2*>(p);
-    v[0] = t.x; v[1] = t.y;
-  } else if constexpr (VEC && KC == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = t[k];
-  } else {
-#pragma unroll
-    for (int k = 0; k < KC; ++k) v[k] = p[k * sk];
-  }
-}
-template <int KC, bool VEC>
-__device__ __forceinline__ void pix_store(float* __restrict__ p, int64_t sk, const float* v) {
-  if constexpr (VEC && KC == 2) {
-    *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
-  } else if constexpr (VEC && KC == 4) {
-    *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
-  } else {
-#pragma unroll
-    for (int k = 0; k < KC; ++k) p[k * sk] = v[k];
-  }
-}
 
 // lse[m] = logsumexp_k x[m][k]; partial[blk] = {sum w[t] (lse - x[t]), sum w[t]} over the block's kept pixels
 template <int KC, bool VEC>
@@ -60,8 +25,8 @@ __global__ __launch_bounds__(256) void pixel_ce_fwd_kernel(const float* __restri
                                                            const int64_t* __restrict__ labels, int64_t ignore_index,
                                                            const float* __restrict__ weight,
                                                            float* __restrict__ lse, float* __restrict__ partial) {
-  __shared__ float sh[2][4];
-  float sl = 0.f, sw = 0.f;
+  __shared__ float shf[8];
+  float ce[2] = {0.f, 0.f};   // {sum w nll, sum w}
   for (int64_t m = blockIdx.x * (int64_t)256 + threadIdx.x; m < M; m += (int64_t)gridDim.x * 256) {
     const int64_t n = m / HW, p = m - n * HW;
     const float* x = logits + n * st.sn + p * st.sp;
@@ -71,65 +36,25 @@ __global__ __launch_bounds__(256) void pixel_ce_fwd_kernel(const float* __restri
     if constexpr (KC > 0) {
       float v[KC];
       pix_load<KC, VEC>(x, st.sk, v);
-      float mx = v[0];
-#pragma unroll
-      for (int k = 1; k < KC; ++k) mx = fmaxf(mx, v[k]);
-      float s = 0.f;
-#pragma unroll
-      for (int k = 0; k < KC; ++k) {
-        s += __expf(v[k] - mx);
-        xt = (int64_t)k == lab ? v[k] : xt;
-      }
-      l = mx + __logf(s);
+      const PixSoftmax r = pix_softmax_reg<KC>(v, lab);
+      l = r.mx + __logf(r.s);
+      xt = r.xt;
     } else {
-      float mx = x[0], s = 1.f;
-      for (int k = 1; k < K; ++k) {
-        const float xv = x[k * st.sk];
-        if (xv > mx) {
-          s = s * __expf(mx - xv) + 1.f;
-          mx = xv;
-        } else {
-          s += __expf(xv - mx);
-        }
-      }
-      l = mx + __logf(s);
+      l = pix_online_lse(x, st.sk, K);
       if (keep) xt = x[lab * st.sk];
     }
     lse[m] = l;
-    if (keep) {
-      const float w = weight ? weight[lab] : 1.f;
-      sl += w * (l - xt);
-      sw += w;
-    }
+    if (keep) pix_ce_add(ce, weight, lab, l, xt);
   }
-  sl = warp_sum(sl);
-  sw = warp_sum(sw);
-  const int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sh[0][wv] = sl; sh[1][wv] = sw; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    partial[2 * blockIdx.x] = sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3];
-    partial[2 * blockIdx.x + 1] = sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3];
-  }
+  pix_ce_block_store(ce, shf, partial + 2 * blockIdx.x);
 }
 
 // Class-last ([M][K] contiguous) logits with K > 4.  A lane that walks its own pixel's K floats makes
 // every load of the wave touch 64 cache lines (4 bytes used of each), and the lines are evicted before
 // the next class reads them (K = 21: several times slower than a plain read of the same bytes,
 // benchmarks/multiclass_bench.py times both through dlmpi_set_pixel_tiles).  So a block
-// stages P pixels (P * K contiguous floats, 16-byte loads) in LDS and each of the first P threads
-// reduces its row from there.  Thread t starts its row at class t % K, so rows of an even length do
-// not collide on LDS banks; the order is fixed per thread, hence still reproducible.
-__device__ __forceinline__ void pix_tile_load(float* __restrict__ tile, const float* __restrict__ src, int nf) {
-  for (int i = threadIdx.x * 4; i < nf; i += 1024) {
-    if (i + 4 <= nf) {
-      *reinterpret_cast<f32x4*>(tile + i) = *reinterpret_cast<const f32x4*>(src + i);
-    } else {
-      for (int e = 0; i + e < nf; ++e) tile[i + e] = src[i + e];
-    }
-  }
-}
-
+// stages P pixels (P * K contiguous floats, 16-byte loads: tiles start 16-byte aligned here, phase 0) in
+// LDS and each of the first P threads reduces its row from there (pix_row_lse).
 __global__ __launch_bounds__(256) void pixel_ce_fwd_tile_kernel(const float* __restrict__ logits, int K, int P,
                                                                 int64_t M, const int64_t* __restrict__ labels,
                                                                 int64_t ignore_index,
@@ -137,49 +62,26 @@ __global__ __launch_bounds__(256) void pixel_ce_fwd_tile_kernel(const float* __r
                                                                 float* __restrict__ lse,
                                                                 float* __restrict__ partial) {
   extern __shared__ __align__(16) float tile[];
-  __shared__ float sh[2][4];
-  float sl = 0.f, sw = 0.f;
+  __shared__ float shf[8];
+  float ce[2] = {0.f, 0.f};
   const int64_t ntiles = (M + P - 1) / P;
   const int k0 = threadIdx.x % K;
   for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const int64_t m0 = t * P;
     const int np = (int)(M - m0 < P ? M - m0 : P);
-    pix_tile_load(tile, logits + m0 * K, np * K);
+    pix_tile_copy<true>(tile, const_cast<float*>(logits + m0 * K), np * K, 0);
     __syncthreads();
     if ((int)threadIdx.x < np) {
       const float* row = tile + threadIdx.x * K;
-      float mx = -INFINITY;
-      int kk = k0;
-      for (int k = 0; k < K; ++k) {
-        mx = fmaxf(mx, row[kk]);
-        kk = kk + 1 == K ? 0 : kk + 1;
-      }
-      float s = 0.f;
-      for (int k = 0; k < K; ++k) {
-        s += __expf(row[kk] - mx);
-        kk = kk + 1 == K ? 0 : kk + 1;
-      }
-      const float l = mx + __logf(s);
+      const float l = pix_row_lse(row, K, k0);
       const int64_t m = m0 + threadIdx.x;
       const int64_t lab = labels[m];
       lse[m] = l;
-      if (pix_kept(lab, K, ignore_index)) {
-        const float w = weight ? weight[lab] : 1.f;
-        sl += w * (l - row[lab]);
-        sw += w;
-      }
+      if (pix_kept(lab, K, ignore_index)) pix_ce_add(ce, weight, lab, l, row[lab]);
     }
     __syncthreads();
   }
-  sl = warp_sum(sl);
-  sw = warp_sum(sw);
-  const int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sh[0][wv] = sl; sh[1][wv] = sw; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    partial[2 * blockIdx.x] = sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3];
-    partial[2 * blockIdx.x + 1] = sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3];
-  }
+  pix_ce_block_store(ce, shf, partial + 2 * blockIdx.x);
 }
 
 // the backward through the same tiles: the row is turned into its gradient in LDS and stored with 16-byte stores
@@ -199,7 +101,7 @@ __global__ __launch_bounds__(256) void pixel_ce_bwd_tile_kernel(const float* __r
     const int64_t m0 = t * P;
     const int np = (int)(M - m0 < P ? M - m0 : P);
     const int nf = np * K;
-    pix_tile_load(tile, logits + m0 * K, nf);
+    pix_tile_copy<true>(tile, const_cast<float*>(logits + m0 * K), nf, 0);
     __syncthreads();
     if ((int)threadIdx.x < np) {
       float* row = tile + threadIdx.x * K;
@@ -211,24 +113,14 @@ __global__ __launch_bounds__(256) void pixel_ce_bwd_tile_kernel(const float* __r
         const float l = lse[m];
         for (int k = 0; k < K; ++k) {
           row[kk] = (__expf(row[kk] - l) - ((int64_t)kk == lab ? 1.f : 0.f)) * g;
-          kk = kk + 1 == K ? 0 : kk + 1;
+          kk = pix_row_next(kk, K);
         }
       } else {
-        for (int k = 0; k < K; ++k) {
-          row[kk] = 0.f;
-          kk = kk + 1 == K ? 0 : kk + 1;
-        }
+        pix_row_zero(row, K, k0);
       }
     }
     __syncthreads();
-    float* dst = dlogits + m0 * K;
-    for (int i = threadIdx.x * 4; i < nf; i += 1024) {
-      if (i + 4 <= nf) {
-        *reinterpret_cast<f32x4*>(dst + i) = *reinterpret_cast<const f32x4*>(tile + i);
-      } else {
-        for (int e = 0; i + e < nf; ++e) dst[i + e] = tile[i + e];
-      }
-    }
+    pix_tile_copy<false>(tile, dlogits + m0 * K, nf, 0);
     __syncthreads();
   }
 }
@@ -364,32 +256,8 @@ extern "C" int dlmpi_pixel_ce_blocks(int64_t M) { return (int)pix_blocks(M); }
 
 static bool pix_args_ok(int K, int64_t HW, int N) { return K >= 2 && K <= 256 && HW > 0 && N > 0; }
 
-// vector access of a pixel's K logits: class stride 1, pixel stride K, and every pixel K*4-byte aligned
-static bool pix_vec_ok(const void* a, const void* b, int K, int64_t sn, int64_t sk, int64_t sp) {
-  if ((K != 2 && K != 4) || sk != 1 || sp != K || sn % K) return false;
-  const uintptr_t al = (uintptr_t)K * 4 - 1;
-  return !((uintptr_t)a & al) && !(b && ((uintptr_t)b & al));
-}
-
-// the LDS-tile kernels: class-last contiguous [M][K] logits, K > 4, 16-byte aligned; pixels per tile (0: no)
-static int g_pix_tiles = 1;
-extern "C" void dlmpi_set_pixel_tiles(int on) { g_pix_tiles = on; }   // 0: the lane-per-pixel kernels everywhere (A/B)
-
-static int pix_tile_pixels(const void* a, const void* b, int K, int64_t HW, int64_t sn, int64_t sk, int64_t sp) {
-  if (!g_pix_tiles || K <= 4 || sk != 1 || sp != K || sn != HW * K) return 0;
-  if (((uintptr_t)a & 15) || (b && ((uintptr_t)b & 15))) return 0;
-  return K <= 32 ? 256 : (8192 / K) & ~3;   // <= 32 KB of LDS, a multiple of 4 pixels: tiles stay 16-byte aligned
-}
-
-#define PIX_DISPATCH(KER, GRID, VECOK, ...)                                                           \
-  do {                                                                                                \
-    if (K == 2 && (VECOK)) hipLaunchKernelGGL((KER<2, true>), GRID, dim3(256), 0, s, __VA_ARGS__);    \
-    else if (K == 4 && (VECOK)) hipLaunchKernelGGL((KER<4, true>), GRID, dim3(256), 0, s, __VA_ARGS__); \
-    else if (K == 2) hipLaunchKernelGGL((KER<2, false>), GRID, dim3(256), 0, s, __VA_ARGS__);         \
-    else if (K == 3) hipLaunchKernelGGL((KER<3, false>), GRID, dim3(256), 0, s, __VA_ARGS__);         \
-    else if (K == 4) hipLaunchKernelGGL((KER<4, false>), GRID, dim3(256), 0, s, __VA_ARGS__);         \
-    else hipLaunchKernelGGL((KER<0, false>), GRID, dim3(256), 0, s, __VA_ARGS__);                     \
-  } while (0)
+// 0: the lane-per-pixel kernels everywhere, here and in seg_dice.hip (A/B; pix_tile_pixels)
+extern "C" void dlmpi_set_pixel_tiles(int on) { g_pix_tiles = on; }
 
 // partial: [dlmpi_pixel_ce_blocks(N * HW)][2] floats; loss, den: one float each
 extern "C" hipError_t dlmpi_pixel_ce_fwd(const float* logits, int64_t sn, int64_t sk, int64_t sp, int N, int K,
@@ -407,7 +275,7 @@ extern "C" hipError_t dlmpi_pixel_ce_fwd(const float* logits, int64_t sn, int64_
                        M, labels, ignore_index, weight, lse, partial);
   else
     PIX_DISPATCH(pixel_ce_fwd_kernel, dim3(nblk), vec, logits, st, K, HW, M, labels, ignore_index, weight, lse,
-               partial);
+                 partial);
   hipLaunchKernelGGL(pixel_ce_finish_kernel, dim3(1), dim3(256), 0, s, partial, (int)nblk, loss, den);
   return hipGetLastError();
 }
@@ -427,7 +295,7 @@ extern "C" hipError_t dlmpi_pixel_ce_bwd(const float* logits, int64_t sn, int64_
                        dlogits);
   else
     PIX_DISPATCH(pixel_ce_bwd_kernel, dim3(ew_blocks_pix(M)), vec, logits, st, K, HW, M, labels, ignore_index, weight,
-               lse, go, den, dlogits);
+                 lse, go, den, dlogits);
   return hipGetLastError();
 }
 

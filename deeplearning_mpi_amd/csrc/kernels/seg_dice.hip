@@ -19,75 +19,13 @@
 // A block never spans two samples.  No float atomics, every reduction in a fixed order: the same bits on
 // every run.  A weight of exactly zero leaves its term out (a NaN cross-entropy of an all-ignored batch
 // does not reach a pure Dice loss).
-#include "common.h"
+// The softmax arithmetic, the addressing, the block reduction and the tile copy are pixel_softmax.h's,
+// shared with pixel_ce.hip: a zero Dice weight is that file's loss, bit for bit.
+#include "pixel_softmax.h"
 
 namespace dlmpi {
 
-struct SegStrides {
-  int64_t sn, sk, sp;   // element strides of sample, class, flat pixel (h * W + w)
-};
-
 constexpr int kDiceBlocksTotal = 2048;   // about N * blocks_x
-
-__device__ __forceinline__ bool dice_kept(int64_t lab, int K, int64_t ignore_index) {
-  return lab != ignore_index && lab >= 0 && lab < K;
-}
-
-__device__ __forceinline__ unsigned warp_sum_u(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
-  return v;
-}
-
-// block-wide sums (4 waves, fixed order) of NF floats and NU counts, returned to every thread;
-// shf: 4 * NF floats, shu: 4 * NU counts of LDS, free again on return
-template <int NF, int NU>
-__device__ __forceinline__ void dice_block_sums(float* f, unsigned* u, float* shf, unsigned* shu) {
-  const int wv = threadIdx.x >> 6;
-  const bool lead = (threadIdx.x & 63) == 0;
-#pragma unroll
-  for (int i = 0; i < NF; ++i) {
-    const float v = warp_sum(f[i]);
-    if (lead) shf[i * 4 + wv] = v;
-  }
-#pragma unroll
-  for (int i = 0; i < NU; ++i) {
-    const unsigned v = warp_sum_u(u[i]);
-    if (lead) shu[i * 4 + wv] = v;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < NF; ++i) f[i] = shf[i * 4] + shf[i * 4 + 1] + shf[i * 4 + 2] + shf[i * 4 + 3];
-#pragma unroll
-  for (int i = 0; i < NU; ++i) u[i] = shu[i * 4] + shu[i * 4 + 1] + shu[i * 4 + 2] + shu[i * 4 + 3];
-  __syncthreads();
-}
-
-template <int KC, bool VEC>
-__device__ __forceinline__ void dice_pix_load(const float* __restrict__ p, int64_t sk, float* v) {
-  if constexpr (VEC && KC == 2) {
-    const float2 t = *reinterpret_cast<const float2*>(p);
-    v[0] = t.x; v[1] = t.y;
-  } else if constexpr (VEC && KC == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = t[k];
-  } else {
-#pragma unroll
-    for (int k = 0; k < KC; ++k) v[k] = p[k * sk];
-  }
-}
-template <int KC, bool VEC>
-__device__ __forceinline__ void dice_pix_store(float* __restrict__ p, int64_t sk, const float* v) {
-  if constexpr (VEC && KC == 2) {
-    *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
-  } else if constexpr (VEC && KC == 4) {
-    *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
-  } else {
-#pragma unroll
-    for (int k = 0; k < KC; ++k) p[k * sk] = v[k];
-  }
-}
 
 // ------------------------------------------------------------------------------------------------
 // forward, a lane per pixel.  KC = 2, 3, 4: the pixel's logits and the per-class sums in registers
@@ -95,7 +33,7 @@ __device__ __forceinline__ void dice_pix_store(float* __restrict__ p, int64_t sk
 // softmax), then one block-reduced {I, P, T} per class that re-reads the block's pixels.
 // part_ce [N][gridDim.x][2], part_d [N][gridDim.x][K][3]
 template <int KC, bool VEC>
-__global__ __launch_bounds__(256) void ce_dice_fwd_kernel(const float* __restrict__ logits, SegStrides st, int K,
+__global__ __launch_bounds__(256) void ce_dice_fwd_kernel(const float* __restrict__ logits, PixStrides st, int K,
                                                           int64_t HW, const int64_t* __restrict__ labels,
                                                           int64_t ignore_index, const float* __restrict__ weight,
                                                           float* lse, float* __restrict__ part_ce,
@@ -113,30 +51,21 @@ __global__ __launch_bounds__(256) void ce_dice_fwd_kernel(const float* __restric
   for (int i = 0; i < 2 * KK + 2; ++i) f[i] = 0.f;
 #pragma unroll
   for (int i = 0; i < KK; ++i) u[i] = 0u;
-  float& sl = f[2 * KK];
-  float& sw = f[2 * KK + 1];
+  float* ce = f + 2 * KK;   // {sum w nll, sum w}
   for (int64_t p = p0; p < HW; p += step) {
     const int64_t m = (int64_t)n * HW + p;
     const float* x = xs + p * st.sp;
     const int64_t lab = labels[m];
-    const bool keep = dice_kept(lab, K, ignore_index);
+    const bool keep = pix_kept(lab, K, ignore_index);
     float l, xt = 0.f;
     if constexpr (KC > 0) {
       float v[KC];
-      dice_pix_load<KC, VEC>(x, st.sk, v);
-      float mx = v[0];
-#pragma unroll
-      for (int k = 1; k < KC; ++k) mx = fmaxf(mx, v[k]);
-      float s = 0.f;
-#pragma unroll
-      for (int k = 0; k < KC; ++k) {
-        xt = (int64_t)k == lab ? v[k] : xt;
-        v[k] = __expf(v[k] - mx);
-        s += v[k];
-      }
-      l = mx + __logf(s);
+      pix_load<KC, VEC>(x, st.sk, v);
+      const PixSoftmax r = pix_softmax_reg<KC>(v, lab);
+      l = r.mx + __logf(r.s);
+      xt = r.xt;
       if (keep) {
-        const float inv = 1.f / s;
+        const float inv = 1.f / r.s;
 #pragma unroll
         for (int k = 0; k < KC; ++k) {
           const float pk = v[k] * inv;
@@ -147,28 +76,14 @@ __global__ __launch_bounds__(256) void ce_dice_fwd_kernel(const float* __restric
         }
       }
     } else {
-      float mx = x[0], s = 1.f;
-      for (int k = 1; k < K; ++k) {
-        const float xv = x[k * st.sk];
-        if (xv > mx) {
-          s = s * __expf(mx - xv) + 1.f;
-          mx = xv;
-        } else {
-          s += __expf(xv - mx);
-        }
-      }
-      l = mx + __logf(s);
+      l = pix_online_lse(x, st.sk, K);
       if (keep) xt = x[lab * st.sk];
     }
     lse[m] = l;
-    if (keep) {
-      const float w = weight ? weight[lab] : 1.f;
-      sl += w * (l - xt);
-      sw += w;
-    }
+    if (keep) pix_ce_add(ce, weight, lab, l, xt);
   }
   if constexpr (KC > 0) {
-    dice_block_sums<2 * KC + 2, KC>(f, u, shf, shu);
+    pix_block_sums<2 * KC + 2, KC>(f, u, shf, shu);
     if (threadIdx.x == 0) {
 #pragma unroll
       for (int k = 0; k < KC; ++k) {
@@ -177,23 +92,18 @@ __global__ __launch_bounds__(256) void ce_dice_fwd_kernel(const float* __restric
         q[1] = f[2 * k + 1];
         q[2] = __uint_as_float(u[k]);
       }
-      part_ce[2 * blk] = sl;
-      part_ce[2 * blk + 1] = sw;
-    }
-  } else {
-    float ce[2] = {sl, sw};
-    dice_block_sums<2, 0>(ce, nullptr, shf, shu);
-    if (threadIdx.x == 0) {
       part_ce[2 * blk] = ce[0];
       part_ce[2 * blk + 1] = ce[1];
     }
+  } else {
+    pix_ce_block_store(ce, shf, part_ce + 2 * blk);
     for (int c = 0; c < K; ++c) {
       float a[2] = {0.f, 0.f};
       unsigned t[1] = {0u};
       for (int64_t p = p0; p < HW; p += step) {
         const int64_t m = (int64_t)n * HW + p;
         const int64_t lab = labels[m];
-        if (!dice_kept(lab, K, ignore_index)) continue;
+        if (!pix_kept(lab, K, ignore_index)) continue;
         const float pc = __expf(xs[p * st.sp + c * st.sk] - lse[m]);   // lse[m]: this thread's own store
         a[1] += pc;
         if (lab == c) {
@@ -201,7 +111,7 @@ __global__ __launch_bounds__(256) void ce_dice_fwd_kernel(const float* __restric
           t[0] += 1u;
         }
       }
-      dice_block_sums<2, 1>(a, t, shf, shu);
+      pix_block_sums<2, 1>(a, t, shf, shu);
       if (threadIdx.x == 0) {
         float* q = part_d + (blk * K + c) * 3;
         q[0] = a[0];
@@ -215,28 +125,7 @@ __global__ __launch_bounds__(256) void ce_dice_fwd_kernel(const float* __restric
 // ------------------------------------------------------------------------------------------------
 // Class-last contiguous logits with K > 4: the LDS tiles of pixel_ce.hip, per sample.  A sample's first
 // logit need not be 16-byte aligned (H * W * K odd), so the tile is kept at the source's offset within
-// its 16 bytes: 16-byte copies in between, single floats at the two ends.
-__device__ __forceinline__ int dice_tile_phase(const float* src) { return (int)(((uintptr_t)src >> 2) & 3); }
-
-template <bool LOAD>
-__device__ __forceinline__ void dice_tile_copy(float* __restrict__ tile, float* __restrict__ glob, int nf, int ph) {
-  const int head = min((4 - ph) & 3, nf);
-  const int body = (nf - head) & ~3;
-  if ((int)threadIdx.x < head) {
-    if constexpr (LOAD) tile[threadIdx.x] = glob[threadIdx.x];
-    else glob[threadIdx.x] = tile[threadIdx.x];
-  }
-  for (int i = head + threadIdx.x * 4; i < head + body; i += 1024) {
-    if constexpr (LOAD) *reinterpret_cast<f32x4*>(tile + i) = *reinterpret_cast<const f32x4*>(glob + i);
-    else *reinterpret_cast<f32x4*>(glob + i) = *reinterpret_cast<const f32x4*>(tile + i);
-  }
-  const int i = head + body + threadIdx.x;
-  if (i < nf) {
-    if constexpr (LOAD) tile[i] = glob[i];
-    else glob[i] = tile[i];
-  }
-}
-
+// its 16 bytes (pix_tile_phase, pix_tile_copy).
 // dynamic LDS: tile [P * K + 4] | red [768] | labs [P] | sh [8].  Thread t < np reduces pixel t's row
 // (from class t % K on) and turns it into the row's softmax (zeros if ignored); then thread (g, c) =
 // (t / K, t % K), g < G = 256 / K, sums class c over the pixels g, g + G, ..., and thread c < K adds the G
@@ -251,7 +140,7 @@ __global__ __launch_bounds__(256) void ce_dice_fwd_tile_kernel(const float* __re
   const int n = blockIdx.y;
   const int64_t blk = (int64_t)n * gridDim.x + blockIdx.x;
   const float* base = logits + (int64_t)n * HW * K;
-  const int ph = dice_tile_phase(base);
+  const int ph = pix_tile_phase(base);
   float* tile = smem + ph;
   float* red = smem + P * K + 4;
   int* labs = reinterpret_cast<int*>(red + 768);
@@ -265,39 +154,24 @@ __global__ __launch_bounds__(256) void ce_dice_fwd_tile_kernel(const float* __re
   for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const int64_t q0 = t * P;
     const int np = (int)(HW - q0 < P ? HW - q0 : P);
-    dice_tile_copy<true>(tile, const_cast<float*>(base + q0 * K), np * K, ph);
+    pix_tile_copy<true>(tile, const_cast<float*>(base + q0 * K), np * K, ph);
     __syncthreads();
     if ((int)threadIdx.x < np) {
       float* row = tile + threadIdx.x * K;
-      float mx = -INFINITY;
-      int kk = c;
-      for (int k = 0; k < K; ++k) {
-        mx = fmaxf(mx, row[kk]);
-        kk = kk + 1 == K ? 0 : kk + 1;
-      }
-      float s = 0.f;
-      for (int k = 0; k < K; ++k) {
-        s += __expf(row[kk] - mx);
-        kk = kk + 1 == K ? 0 : kk + 1;
-      }
-      const float l = mx + __logf(s);
+      const float l = pix_row_lse(row, K, c);
       const int64_t m = (int64_t)n * HW + q0 + threadIdx.x;
       const int64_t lab = labels[m];
       lse[m] = l;
-      if (dice_kept(lab, K, ignore_index)) {
-        const float w = weight ? weight[lab] : 1.f;
-        ce[0] += w * (l - row[lab]);
-        ce[1] += w;
+      if (pix_kept(lab, K, ignore_index)) {
+        pix_ce_add(ce, weight, lab, l, row[lab]);
+        int kk = c;
         for (int k = 0; k < K; ++k) {
           row[kk] = __expf(row[kk] - l);
-          kk = kk + 1 == K ? 0 : kk + 1;
+          kk = pix_row_next(kk, K);
         }
         labs[threadIdx.x] = (int)lab;
       } else {
-        for (int k = 0; k < K; ++k) {
-          row[kk] = 0.f;
-          kk = kk + 1 == K ? 0 : kk + 1;
-        }
+        pix_row_zero(row, K, c);
         labs[threadIdx.x] = -1;
       }
     }
@@ -334,11 +208,7 @@ __global__ __launch_bounds__(256) void ce_dice_fwd_tile_kernel(const float* __re
     q[2] = __uint_as_float(accT);
   }
   __syncthreads();
-  dice_block_sums<2, 0>(ce, nullptr, shf, nullptr);
-  if (threadIdx.x == 0) {
-    part_ce[2 * blk] = ce[0];
-    part_ce[2 * blk + 1] = ce[1];
-  }
+  pix_ce_block_store(ce, shf, part_ce + 2 * blk);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -419,7 +289,7 @@ __global__ __launch_bounds__(1024) void ce_dice_finish_kernel(const float* __res
 // ------------------------------------------------------------------------------------------------
 // backward, a lane per pixel; the sample's {A, B} rows (times go) in registers (KC > 0) or LDS
 template <int KC, bool VEC>
-__global__ __launch_bounds__(256) void ce_dice_bwd_kernel(const float* __restrict__ logits, SegStrides st, int K,
+__global__ __launch_bounds__(256) void ce_dice_bwd_kernel(const float* __restrict__ logits, PixStrides st, int K,
                                                           int64_t HW, const int64_t* __restrict__ labels,
                                                           int64_t ignore_index, const float* __restrict__ weight,
                                                           const float* __restrict__ lse,
@@ -448,13 +318,13 @@ __global__ __launch_bounds__(256) void ce_dice_bwd_kernel(const float* __restric
     const int64_t m = (int64_t)n * HW + p;
     const int64_t off = (int64_t)n * st.sn + p * st.sp;
     const int64_t lab = labels[m];
-    const bool keep = dice_kept(lab, K, ignore_index);
+    const bool keep = pix_kept(lab, K, ignore_index);
     const float l = lse[m];
     const float wc = keep ? cg * (weight ? weight[lab] : 1.f) : 0.f;
     if constexpr (KC > 0) {
       float v[KC];
       if (keep) {
-        dice_pix_load<KC, VEC>(logits + off, st.sk, v);
+        pix_load<KC, VEC>(logits + off, st.sk, v);
         float dot = 0.f;
 #pragma unroll
         for (int k = 0; k < KC; ++k) {
@@ -470,7 +340,7 @@ __global__ __launch_bounds__(256) void ce_dice_bwd_kernel(const float* __restric
 #pragma unroll
         for (int k = 0; k < KC; ++k) v[k] = 0.f;
       }
-      dice_pix_store<KC, VEC>(dlogits + off, st.sk, v);
+      pix_store<KC, VEC>(dlogits + off, st.sk, v);
     } else {
       if (keep) {
         float dot = 0.f;
@@ -505,7 +375,7 @@ __global__ __launch_bounds__(256) void ce_dice_bwd_tile_kernel(const float* __re
   const int n = blockIdx.y;
   const float* base = logits + (int64_t)n * HW * K;
   float* dbase = dlogits + (int64_t)n * HW * K;
-  const int ph = dice_tile_phase(base);   // dlogits: the same offset within 16 bytes (checked by the launcher)
+  const int ph = pix_tile_phase(base);   // dlogits: the same offset within 16 bytes (checked by the launcher)
   float* tile = smem + ph;
   float* stab = smem + P * K + 4;
   const float g0 = go ? *go : 1.f;
@@ -517,14 +387,14 @@ __global__ __launch_bounds__(256) void ce_dice_bwd_tile_kernel(const float* __re
     const int64_t q0 = t * P;
     const int np = (int)(HW - q0 < P ? HW - q0 : P);
     const int nf = np * K;
-    dice_tile_copy<true>(tile, const_cast<float*>(base + q0 * K), nf, ph);
+    pix_tile_copy<true>(tile, const_cast<float*>(base + q0 * K), nf, ph);
     __syncthreads();   // (also orders the stab stores before their first use)
     if ((int)threadIdx.x < np) {
       float* row = tile + threadIdx.x * K;
       const int64_t m = (int64_t)n * HW + q0 + threadIdx.x;
       const int64_t lab = labels[m];
       int kk = k0;
-      if (dice_kept(lab, K, ignore_index)) {
+      if (pix_kept(lab, K, ignore_index)) {
         const float wc = cg * (weight ? weight[lab] : 1.f);
         const float l = lse[m];
         float dot = 0.f;
@@ -532,7 +402,7 @@ __global__ __launch_bounds__(256) void ce_dice_bwd_tile_kernel(const float* __re
           const float pk = __expf(row[kk] - l);
           row[kk] = pk;
           dot += pk * stab[2 * kk + 1];
-          kk = kk + 1 == K ? 0 : kk + 1;
+          kk = pix_row_next(kk, K);
         }
         const float al = stab[2 * (int)lab];
         dot += row[lab] * al;
@@ -540,17 +410,14 @@ __global__ __launch_bounds__(256) void ce_dice_bwd_tile_kernel(const float* __re
           const float pk = row[kk];
           const bool hit = (int64_t)kk == lab;
           row[kk] = pk * (stab[2 * kk + 1] + (hit ? al : 0.f) - dot) + (pk - (hit ? 1.f : 0.f)) * wc;
-          kk = kk + 1 == K ? 0 : kk + 1;
+          kk = pix_row_next(kk, K);
         }
       } else {
-        for (int k = 0; k < K; ++k) {
-          row[kk] = 0.f;
-          kk = kk + 1 == K ? 0 : kk + 1;
-        }
+        pix_row_zero(row, K, k0);
       }
     }
     __syncthreads();
-    dice_tile_copy<false>(tile, dbase + q0 * K, nf, ph);
+    pix_tile_copy<false>(tile, dbase + q0 * K, nf, ph);
     __syncthreads();
   }
 }
@@ -575,7 +442,7 @@ __global__ __launch_bounds__(256) void bce_dice_fwd_kernel(const float* __restri
     f[2] += pr;
     f[3] += tv;
   }
-  dice_block_sums<4, 0>(f, nullptr, shf, nullptr);
+  pix_block_sums<4, 0>(f, nullptr, shf, nullptr);
   if (threadIdx.x == 0) {
     float* q = part + ((int64_t)n * gridDim.x + blockIdx.x) * 4;
     q[0] = f[0]; q[1] = f[1]; q[2] = f[2]; q[3] = f[3];
@@ -665,29 +532,6 @@ static bool dice_weights_ok(float a, float b, float smooth) {
          smooth <= 3.0e38f;
 }
 
-static bool dice_vec_ok(const void* a, const void* b, int K, int64_t sn, int64_t sk, int64_t sp) {
-  if ((K != 2 && K != 4) || sk != 1 || sp != K || sn % K) return false;
-  const uintptr_t al = (uintptr_t)K * 4 - 1;
-  return !((uintptr_t)a & al) && !(b && ((uintptr_t)b & al));
-}
-
-// the LDS-tile kernels: class-last contiguous [N][HW][K] logits, K > 4, 16-byte aligned bases; pixels per tile (0: no)
-static int dice_tile_pixels(const void* a, const void* b, int K, int64_t HW, int64_t sn, int64_t sk, int64_t sp) {
-  if (K <= 4 || sk != 1 || sp != K || sn != HW * K) return 0;
-  if (((uintptr_t)a & 15) || (b && ((uintptr_t)b & 15))) return 0;
-  return K <= 32 ? 256 : (8192 / K) & ~3;   // <= 32 KB of tile, a multiple of 4 pixels
-}
-
-#define DICE_DISPATCH(KER, GRID, VECOK, ...)                                                          \
-  do {                                                                                                \
-    if (K == 2 && (VECOK)) hipLaunchKernelGGL((KER<2, true>), GRID, dim3(256), 0, s, __VA_ARGS__);    \
-    else if (K == 4 && (VECOK)) hipLaunchKernelGGL((KER<4, true>), GRID, dim3(256), 0, s, __VA_ARGS__); \
-    else if (K == 2) hipLaunchKernelGGL((KER<2, false>), GRID, dim3(256), 0, s, __VA_ARGS__);         \
-    else if (K == 3) hipLaunchKernelGGL((KER<3, false>), GRID, dim3(256), 0, s, __VA_ARGS__);         \
-    else if (K == 4) hipLaunchKernelGGL((KER<4, false>), GRID, dim3(256), 0, s, __VA_ARGS__);         \
-    else hipLaunchKernelGGL((KER<0, false>), GRID, dim3(256), 0, s, __VA_ARGS__);                     \
-  } while (0)
-
 // gx = dlmpi_seg_dice_blocks(HW, N); part_ce [N][gx][2], part_d [N][gx][K][3], tab [N][K][2]; loss, den: one float each
 extern "C" hipError_t dlmpi_pixel_ce_dice_fwd(const float* logits, int64_t sn, int64_t sk, int64_t sp, int N, int K,
                                               int64_t HW, const int64_t* labels, int64_t ignore_index,
@@ -698,15 +542,14 @@ extern "C" hipError_t dlmpi_pixel_ce_dice_fwd(const float* logits, int64_t sn, i
     return hipErrorInvalidValue;
   const unsigned gx = (unsigned)dlmpi_seg_dice_blocks(HW, N);
   const dim3 grid(gx, (unsigned)N);
-  const SegStrides st{sn, sk, sp};
-  const bool vec = dice_vec_ok(logits, nullptr, K, sn, sk, sp);
-  const int P = dice_tile_pixels(logits, nullptr, K, HW, sn, sk, sp);
+  const PixStrides st{sn, sk, sp};
+  const bool vec = pix_vec_ok(logits, nullptr, K, sn, sk, sp);
+  const int P = pix_tile_pixels(logits, nullptr, K, HW, sn, sk, sp);
   if (P > 0)
     hipLaunchKernelGGL(ce_dice_fwd_tile_kernel, grid, dim3(256), ((size_t)P * K + 4 + 768 + P + 8) * sizeof(float), s,
                        logits, K, P, HW, labels, ignore_index, weight, lse, part_ce, part_d);
   else
-    DICE_DISPATCH(ce_dice_fwd_kernel, grid, vec, logits, st, K, HW, labels, ignore_index, weight, lse, part_ce,
-                  part_d);
+    PIX_DISPATCH(ce_dice_fwd_kernel, grid, vec, logits, st, K, HW, labels, ignore_index, weight, lse, part_ce, part_d);
   hipLaunchKernelGGL(ce_dice_finish_kernel, dim3(1), dim3(1024), 0, s, part_ce, part_d, N, (int)gx, K,
                      include_background ? 0 : 1, smooth, ce_weight, dice_weight, loss, den, tab);
   return hipGetLastError();
@@ -719,15 +562,15 @@ extern "C" hipError_t dlmpi_pixel_ce_dice_bwd(const float* logits, int64_t sn, i
                                               hipStream_t s) {
   if (K < 2 || !dice_args_ok(K, HW, N) || !den || !tab || !(ce_weight >= 0.f)) return hipErrorInvalidValue;
   const dim3 grid((unsigned)dlmpi_seg_dice_blocks(HW, N), (unsigned)N);
-  const SegStrides st{sn, sk, sp};
-  const bool vec = dice_vec_ok(logits, dlogits, K, sn, sk, sp);
-  const int P = dice_tile_pixels(logits, dlogits, K, HW, sn, sk, sp);
+  const PixStrides st{sn, sk, sp};
+  const bool vec = pix_vec_ok(logits, dlogits, K, sn, sk, sp);
+  const int P = pix_tile_pixels(logits, dlogits, K, HW, sn, sk, sp);
   if (P > 0)
     hipLaunchKernelGGL(ce_dice_bwd_tile_kernel, grid, dim3(256), ((size_t)P * K + 4 + 512) * sizeof(float), s, logits,
                        K, P, HW, labels, ignore_index, weight, lse, go, den, tab, ce_weight, dlogits);
   else
-    DICE_DISPATCH(ce_dice_bwd_kernel, grid, vec, logits, st, K, HW, labels, ignore_index, weight, lse, go, den, tab,
-                  ce_weight, dlogits);
+    PIX_DISPATCH(ce_dice_bwd_kernel, grid, vec, logits, st, K, HW, labels, ignore_index, weight, lse, go, den, tab,
+                 ce_weight, dlogits);
   return hipGetLastError();
 }
 

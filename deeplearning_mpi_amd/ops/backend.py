@@ -462,23 +462,28 @@ class NativeBackend:
         self.C.softmax_ce_bwd(logits, logits.stride(0), labels, lse, N, K, K, go, 1.0 / N, d)
         return d
 
+    def _pixel_fwd_out(self, logits):   # what every pixel-loss forward fills: lse [N*H*W], loss (scalar), den [1]
+        lse = torch.empty(logits.numel() // logits.shape[1], dtype=torch.float32, device=logits.device)
+        return lse, lse.new_empty(()), lse.new_empty(1)
+
+    def _pixel_dlogits(self, logits):   # the gradient's buffer, in the strides of the logits
+        d = torch.empty_like(logits)   # dense input: same strides
+        assert d.stride() == logits.stride(), (d.stride(), logits.stride())
+        return d
+
     def pixel_ce_fwd(self, logits, labels, weight=None, ignore_index=-100):
         """logits fp32 [N, K, H, W] in one of the two native layouts (pixel_strides), labels int64
         [N, H, W] -> (loss, per-pixel logsumexp [N*H*W], sum of the kept pixels' weights)."""
         N, K, H, W = logits.shape
+        lse, loss, den = self._pixel_fwd_out(logits)
         st = pixel_strides(logits)
-        dev = logits.device
-        lse = torch.empty(N * H * W, dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        den = torch.empty(1, dtype=torch.float32, device=dev)
         self.C.pixel_ce_fwd(logits, *st, N, K, H * W, labels, int(ignore_index), weight, lse, loss, den)
         return loss, lse, den
 
     def pixel_ce_bwd(self, logits, labels, lse, den, go, weight=None, ignore_index=-100):
         """dlogits in the strides of logits, scaled by go / den on the device."""
         N, K, H, W = logits.shape
-        d = torch.empty_like(logits)   # dense input: same strides
-        assert d.stride() == logits.stride(), (d.stride(), logits.stride())
+        d = self._pixel_dlogits(logits)
         self.C.pixel_ce_bwd(logits, *pixel_strides(logits), N, K, H * W, labels, int(ignore_index), weight, lse, go,
                             den, d)
         return d
@@ -495,11 +500,8 @@ class NativeBackend:
         """pixel_ce_fwd with the soft Dice fused in (seg_dice.hip): loss = ce_weight * CE + dice_weight * Dice
         -> (loss, lse [N*H*W], CE denominator, the Dice gradient's table [N, K, 2]); no host sync."""
         N, K, H, W = logits.shape
-        dev = logits.device
-        lse = torch.empty(N * H * W, dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        den = torch.empty(1, dtype=torch.float32, device=dev)
-        tab = torch.empty(N, K, 2, dtype=torch.float32, device=dev)
+        lse, loss, den = self._pixel_fwd_out(logits)
+        tab = torch.empty(N, K, 2, dtype=torch.float32, device=logits.device)
         self.C.pixel_ce_dice_fwd(logits, *pixel_strides(logits), N, K, H * W, labels, int(ignore_index), weight,
                                  float(ce_weight), float(dice_weight), float(smooth), bool(include_background), lse,
                                  loss, den, tab)
@@ -508,8 +510,7 @@ class NativeBackend:
     def pixel_ce_dice_bwd(self, logits, labels, lse, den, tab, go, weight=None, ignore_index=-100, ce_weight=1.0):
         """dlogits of pixel_ce_dice_fwd's loss in the strides of logits, scaled by go on the device."""
         N, K, H, W = logits.shape
-        d = torch.empty_like(logits)   # dense input: same strides
-        assert d.stride() == logits.stride(), (d.stride(), logits.stride())
+        d = self._pixel_dlogits(logits)
         self.C.pixel_ce_dice_bwd(logits, *pixel_strides(logits), N, K, H * W, labels, int(ignore_index), weight, lse,
                                  go, den, tab, float(ce_weight), d)
         return d

@@ -79,16 +79,20 @@ def _pixel_layout(logits):
     return logits if pixel_strides(logits) is not None else logits.contiguous()
 
 
+def _pixel_inputs(logits, labels, weight):
+    """-> (backend, logits in a native layout, contiguous labels, contiguous weight or None) of a pixel-wise loss."""
+    be = _be(logits.device, logits.dtype)
+    w = weight.to(be.dt).contiguous() if weight is not None else None
+    return be, _pixel_layout(logits).to(be.dt), labels.contiguous(), w
+
+
 class _PixelCE(torch.autograd.Function):
     """Pixel-wise softmax cross-entropy: logits [N, K, H, W] (read in place, no copy), labels int64
     [N, H, W]; the gradient comes back in the strides of the logits."""
 
     @staticmethod
     def forward(ctx, logits, labels, weight, ignore_index):
-        be = _be(logits.device, logits.dtype)
-        x = _pixel_layout(logits).to(be.dt)
-        labels = labels.contiguous()
-        w = weight.to(be.dt).contiguous() if weight is not None else None
+        be, x, labels, w = _pixel_inputs(logits, labels, weight)
         loss, lse, den = be.pixel_ce_fwd(x, labels, w, ignore_index)
         ctx.save_for_backward(x, labels, lse, den, w)
         ctx.ignore_index = ignore_index
@@ -103,12 +107,14 @@ class _PixelCE(torch.autograd.Function):
         return g.to(ctx.in_dtype), None, None, None
 
 
-def _check_pixel_args(logits, labels):
+def _check_pixel_args(logits, labels, weight=None):
     if labels.dim() != 3 or labels.dtype != torch.int64 or labels.shape != logits.shape[:1] + logits.shape[2:]:
         raise ValueError(f"pixel-wise logits {tuple(logits.shape)} need int64 labels [N, H, W], got "
                          f"{labels.dtype} {tuple(labels.shape)}")
     if not 2 <= logits.shape[1] <= 256:
         raise ValueError(f"pixel-wise losses and counts take 2..256 classes, got {logits.shape[1]}")
+    if weight is not None and weight.numel() != logits.shape[1]:
+        raise ValueError(f"weight has {weight.numel()} entries for {logits.shape[1]} classes")
 
 
 def cross_entropy(logits, labels, weight=None, ignore_index=-100):
@@ -116,9 +122,7 @@ def cross_entropy(logits, labels, weight=None, ignore_index=-100):
     [N, K, H, W] logits with [N, H, W] labels: the pixel-wise loss with torch's ``weight`` /
     ``ignore_index`` semantics (labels outside [0, K) are ignored as well)."""
     if logits.dim() == 4:
-        _check_pixel_args(logits, labels)
-        if weight is not None and weight.numel() != logits.shape[1]:
-            raise ValueError(f"weight has {weight.numel()} entries for {logits.shape[1]} classes")
+        _check_pixel_args(logits, labels, weight)
         return _PixelCE.apply(logits, labels, weight, int(ignore_index))
     if weight is not None or ignore_index != -100:
         raise NotImplementedError("weight / ignore_index are implemented for pixel-wise ([N, K, H, W]) logits")
@@ -135,10 +139,7 @@ class _PixelCEDice(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, labels, weight, ignore_index, ce_weight, dice_weight, smooth, include_background):
-        be = _be(logits.device, logits.dtype)
-        x = _pixel_layout(logits).to(be.dt)
-        labels = labels.contiguous()
-        w = weight.to(be.dt).contiguous() if weight is not None else None
+        be, x, labels, w = _pixel_inputs(logits, labels, weight)
         loss, lse, den, tab = be.pixel_ce_dice_fwd(x, labels, w, ignore_index, ce_weight, dice_weight, smooth,
                                                    include_background)
         ctx.save_for_backward(x, labels, lse, den, tab, w)
@@ -197,9 +198,7 @@ def ce_dice_loss(logits, labels, weight=None, ignore_index=-100, ce_weight=1.0, 
     _check_dice_args(ce_weight, dice_weight, smooth, ("ce_weight", "dice_weight"))
     if logits.dim() != 4:
         raise ValueError(f"ce_dice_loss takes [N, K, H, W] logits, got {tuple(logits.shape)}")
-    _check_pixel_args(logits, labels)
-    if weight is not None and weight.numel() != logits.shape[1]:
-        raise ValueError(f"weight has {weight.numel()} entries for {logits.shape[1]} classes")
+    _check_pixel_args(logits, labels, weight)
     if dice_weight == 0:
         loss = _PixelCE.apply(logits, labels, weight, int(ignore_index))
         return loss if ce_weight == 1 else loss * ce_weight
