@@ -13,11 +13,68 @@
 namespace dlmpi_ext {
 
 // --------------------------------- batch norm ----------------------------------------------
+// Argument checks of the BatchNorm family: a few integer compares per call, before anything is
+// launched (no synchronisation, no allocation).  The kernels index by M, C, ld and off alone, so
+// whatever passes here stays inside every operand.
+namespace {
+
+[[noreturn]] void bn_fail(const char* what, const std::string& why) {
+  throw std::runtime_error(std::string(what) + ": " + why);
+}
+
+// the chunked row reductions (bn.hip rowmap): 256 / (C / 8) row lanes per block
+void rowmap_shape(int64_t M, int C, const char* what) {
+  if (C < 8 || C % 8 || C > 2048) bn_fail(what, "C must be a multiple of 8 in [8, 2048]");
+  if (M < 1) bn_fail(what, "M < 1");
+}
+// the elementwise kernels: one thread per 8 channels
+void ew_shape(int64_t M, int C, const char* what) {
+  if (C < 8 || C % 8) bn_fail(what, "C must be a positive multiple of 8");
+  if (M < 1) bn_fail(what, "M < 1");
+}
+// channels [off, off + C) of M rows of a [.][ld] buffer
+void slice_ok(const at::Tensor& t, int64_t M, int C, int ld, int off, const char* what, const char* name) {
+  if (off < 0 || (int64_t)off + C > ld) bn_fail(what, std::string(name) + ": off + C > ld");
+  if (t.numel() < (M - 1) * (int64_t)ld + off + C) bn_fail(what, std::string(name) + ": buffer smaller than the slice");
+}
+void slice_ok(const c10::optional<at::Tensor>& t, int64_t M, int C, int ld, int off, const char* what,
+              const char* name) {
+  if (t.has_value() && t->defined()) slice_ok(*t, M, C, ld, off, what, name);
+}
+// an fp32 tensor of at least n elements (a per-channel vector, the partials)
+void floats_ok(const at::Tensor& t, int64_t n, const char* what, const char* name) {
+  if (t.scalar_type() != at::kFloat) bn_fail(what, std::string(name) + " must be fp32");
+  if (t.numel() < n) bn_fail(what, std::string(name) + " has fewer elements than the launch touches");
+}
+void floats_ok(const c10::optional<at::Tensor>& t, int64_t n, const char* what, const char* name) {
+  if (t.has_value() && t->defined()) floats_ok(*t, n, what, name);
+}
+bool given(const c10::optional<at::Tensor>& t) { return t.has_value() && t->defined(); }
+
+// the column reduce + finalize over partial [T][ns][C]
+void colsum_shape(const at::Tensor& partial, int T, int ns, int C, double count, const char* what) {
+  if (T < 1 || C < 1) bn_fail(what, "needs at least one partial row and one channel");
+  if (!(count >= 1.0)) bn_fail(what, "count < 1");
+  floats_ok(partial, (int64_t)T * ns * C, what, "partial");
+}
+
+}  // namespace
+
 void bn_finalize(const at::Tensor& partial, int ntiles, int C, double count, const c10::optional<at::Tensor>& gamma,
                  const c10::optional<at::Tensor>& beta, const c10::optional<at::Tensor>& running_mean,
                  const c10::optional<at::Tensor>& running_var, double momentum, double eps, at::Tensor scale,
                  at::Tensor shift, const c10::optional<at::Tensor>& save_mean,
                  const c10::optional<at::Tensor>& save_invstd) {
+  colsum_shape(partial, ntiles, 2, C, count, "bn_finalize");
+  floats_ok(gamma, C, "bn_finalize", "gamma");
+  floats_ok(beta, C, "bn_finalize", "beta");
+  if (given(running_mean) != given(running_var)) bn_fail("bn_finalize", "running_mean / running_var come together");
+  floats_ok(running_mean, C, "bn_finalize", "running_mean");
+  floats_ok(running_var, C, "bn_finalize", "running_var");
+  floats_ok(scale, C, "bn_finalize", "scale");
+  floats_ok(shift, C, "bn_finalize", "shift");
+  floats_ok(save_mean, C, "bn_finalize", "save_mean");
+  floats_ok(save_invstd, C, "bn_finalize", "save_invstd");
   at::Tensor ws = colsum_ws(partial, ntiles, C);
   check(dlmpi_bn_finalize(ptr<float>(partial), ntiles, C, count, optr<float>(gamma), optr<float>(beta),
                           optr<float>(running_mean), optr<float>(running_var), (float)momentum, (float)eps,
@@ -26,9 +83,16 @@ void bn_finalize(const at::Tensor& partial, int ntiles, int C, double count, con
         "bn_finalize");
 }
 
-int reduce_blocks(int64_t M, int C) { return dlmpi_reduce_blocks(M, C); }
+int reduce_blocks(int64_t M, int C) {
+  rowmap_shape(M, C, "reduce_blocks");
+  return dlmpi_reduce_blocks(M, C);
+}
 
 void bn_stats(const at::Tensor& x, int64_t M, int C, int ldx, int xoff, at::Tensor partial, int nblk) {
+  rowmap_shape(M, C, "bn_stats");
+  if (nblk < 1) bn_fail("bn_stats", "nblk < 1");
+  slice_ok(x, M, C, ldx, xoff, "bn_stats", "x");
+  floats_ok(partial, (int64_t)nblk * 2 * C, "bn_stats", "partial");
   check(dlmpi_bn_stats(x.data_ptr(), M, C, ldx, xoff, ptr<float>(partial), nblk, act_f32(x, "bn_stats"), cur_stream()),
         "bn_stats");
 }
@@ -37,10 +101,18 @@ void bn_apply(const at::Tensor& x, int ldx, int xoff, int64_t M, int C, const at
               const at::Tensor& shift, const c10::optional<at::Tensor>& res, int ldres, int resoff, bool relu,
               at::Tensor y, int ldy, int yoff, const c10::optional<at::Tensor>& mbits,
               const c10::optional<at::Tensor>& rscale, const c10::optional<at::Tensor>& rshift) {
+  ew_shape(M, C, "bn_apply");
   if (mbits && mbits->numel() != M * (C / 8)) throw std::runtime_error("bn_apply: mask bits must be [M][C/8]");
   if (rscale.has_value() != rshift.has_value() || (rscale && !res))
     throw std::runtime_error("bn_apply: rscale / rshift come together, with a residual");
   if (rscale && (rscale->numel() < C || rshift->numel() < C)) throw std::runtime_error("bn_apply: rscale / rshift < C");
+  slice_ok(x, M, C, ldx, xoff, "bn_apply", "x");
+  slice_ok(res, M, C, ldres, resoff, "bn_apply", "res");
+  slice_ok(y, M, C, ldy, yoff, "bn_apply", "y");
+  floats_ok(scale, C, "bn_apply", "scale");
+  floats_ok(shift, C, "bn_apply", "shift");
+  floats_ok(rscale, C, "bn_apply", "rscale");
+  floats_ok(rshift, C, "bn_apply", "rshift");
   same_type(x, y, "bn_apply y");
   same_type(x, res, "bn_apply res");
   check(dlmpi_bn_apply2(x.data_ptr(), ldx, xoff, M, C, ptr<float>(scale), ptr<float>(shift), optr<uint16_t>(res), ldres,
@@ -53,6 +125,15 @@ void bn_bwd_reduce(const at::Tensor& dy, int lddy, int dyoff, const c10::optiona
                    int ymoff, const c10::optional<at::Tensor>& x, int ldx, int xoff, int64_t M, int C,
                    const c10::optional<at::Tensor>& mean, const c10::optional<at::Tensor>& invstd, at::Tensor partial,
                    int nblk) {
+  rowmap_shape(M, C, "bn_bwd_reduce");
+  if (nblk < 1) bn_fail("bn_bwd_reduce", "nblk < 1");
+  if (given(x) && !(given(mean) && given(invstd))) bn_fail("bn_bwd_reduce", "x needs mean and invstd");
+  slice_ok(dy, M, C, lddy, dyoff, "bn_bwd_reduce", "dy");
+  slice_ok(ymask, M, C, ldym, ymoff, "bn_bwd_reduce", "ymask");
+  slice_ok(x, M, C, ldx, xoff, "bn_bwd_reduce", "x");
+  floats_ok(mean, C, "bn_bwd_reduce", "mean");
+  floats_ok(invstd, C, "bn_bwd_reduce", "invstd");
+  floats_ok(partial, (int64_t)nblk * 2 * C, "bn_bwd_reduce", "partial");
   same_type(dy, ymask, "bn_bwd_reduce ymask");
   same_type(dy, x, "bn_bwd_reduce x");
   check(dlmpi_bn_bwd_reduce(dy.data_ptr(), lddy, dyoff, optr<uint16_t>(ymask), ldym, ymoff, optr<uint16_t>(x), ldx,
@@ -61,10 +142,26 @@ void bn_bwd_reduce(const at::Tensor& dy, int lddy, int dyoff, const c10::optiona
         "bn_bwd_reduce");
 }
 
+// the per-channel operands of both backward finalizes (fin_bwd reads mean and invstd for coef and for raw_z)
+static void bwd_fin_vectors(int C, bool raw_z, const c10::optional<at::Tensor>& gamma,
+                            const c10::optional<at::Tensor>& mean, const c10::optional<at::Tensor>& invstd,
+                            const c10::optional<at::Tensor>& dgamma, const c10::optional<at::Tensor>& dbeta,
+                            const c10::optional<at::Tensor>& coef, const char* what) {
+  if ((given(coef) || raw_z) && !(given(mean) && given(invstd))) bn_fail(what, "coef needs mean and invstd");
+  floats_ok(gamma, C, what, "gamma");
+  floats_ok(mean, C, what, "mean");
+  floats_ok(invstd, C, what, "invstd");
+  floats_ok(dgamma, C, what, "dgamma");
+  floats_ok(dbeta, C, what, "dbeta");
+  floats_ok(coef, 3 * (int64_t)C, what, "coef");
+}
+
 void bn_bwd_finalize(const at::Tensor& partial, int nblk, int C, double count, const c10::optional<at::Tensor>& gamma,
                      const c10::optional<at::Tensor>& mean, const c10::optional<at::Tensor>& invstd,
                      const c10::optional<at::Tensor>& dgamma, const c10::optional<at::Tensor>& dbeta,
                      const c10::optional<at::Tensor>& coef) {
+  colsum_shape(partial, nblk, 2, C, count, "bn_bwd_finalize");
+  bwd_fin_vectors(C, false, gamma, mean, invstd, dgamma, dbeta, coef, "bn_bwd_finalize");
   at::Tensor ws = colsum_ws(partial, nblk, C);
   check(dlmpi_bn_bwd_finalize(ptr<float>(partial), nblk, C, count, optr<float>(gamma), optr<float>(mean),
                               optr<float>(invstd), optr<float>(dgamma), optr<float>(dbeta), optr<float>(coef),
@@ -77,8 +174,12 @@ void bn_bwd_finalize_fused(const at::Tensor& partial, int k2, int C, double coun
                            const c10::optional<at::Tensor>& gamma, const at::Tensor& mean, const at::Tensor& invstd,
                            const c10::optional<at::Tensor>& dgamma, const c10::optional<at::Tensor>& dbeta,
                            const c10::optional<at::Tensor>& coef) {
+  if (partial.dim() != 3) throw std::runtime_error("bn_bwd_finalize_fused: partial must be [tiles][ns][C]");
   const int T = (int)partial.size(0), ns = (int)partial.size(1);
   if (partial.size(2) != C) throw std::runtime_error("bn_bwd_finalize_fused: channel mismatch");
+  if (ns < 2 || ns > 3 || k2 < 1 || k2 >= ns) bn_fail("bn_bwd_finalize_fused", "ns in {2, 3} and 1 <= k2 < ns");
+  colsum_shape(partial, T, ns, C, count, "bn_bwd_finalize_fused");
+  bwd_fin_vectors(C, true, gamma, mean, invstd, dgamma, dbeta, coef, "bn_bwd_finalize_fused");
   at::Tensor ws = colsum_ws(partial, T, C);
   check(dlmpi_bn_bwd_finalize_ex(ptr<float>(partial), T, ns, k2, 1, C, count, optr<float>(gamma), ptr<float>(mean),
                                  ptr<float>(invstd), optr<float>(dgamma), optr<float>(dbeta), optr<float>(coef),
@@ -89,6 +190,13 @@ void bn_bwd_finalize_fused(const at::Tensor& partial, int k2, int C, double coun
 void bn_bwd_apply(const at::Tensor& dy, int lddy, int dyoff, const c10::optional<at::Tensor>& ymask, int ldym,
                   int ymoff, const at::Tensor& x, int ldx, int xoff, int64_t M, int C, const at::Tensor& coef,
                   at::Tensor dx, const c10::optional<at::Tensor>& dyr_out) {
+  ew_shape(M, C, "bn_bwd_apply");
+  slice_ok(dy, M, C, lddy, dyoff, "bn_bwd_apply", "dy");
+  slice_ok(ymask, M, C, ldym, ymoff, "bn_bwd_apply", "ymask");
+  slice_ok(x, M, C, ldx, xoff, "bn_bwd_apply", "x");
+  slice_ok(dx, M, C, C, 0, "bn_bwd_apply", "dx");
+  slice_ok(dyr_out, M, C, C, 0, "bn_bwd_apply", "dyr_out");
+  floats_ok(coef, 3 * (int64_t)C, "bn_bwd_apply", "coef");
   same_type(dy, ymask, "bn_bwd_apply ymask");
   same_type(dy, x, "bn_bwd_apply x");
   same_type(dy, dx, "bn_bwd_apply dx");
@@ -102,8 +210,9 @@ void bn_bwd_apply(const at::Tensor& dy, int lddy, int dyoff, const c10::optional
 // w2 [C][2K] = {wT * coef[0], wT * coef[1]}, b [C] = wT . coef[2]: the dual 1x1 data gradient (bn.hip)
 void dual_dgrad_weights(const at::Tensor& wT, int C, int K, const at::Tensor& coef, at::Tensor w2, at::Tensor b) {
   same_type(wT, w2, "dual_dgrad_weights w2");
-  if (wT.numel() < (int64_t)C * K || w2.numel() < (int64_t)C * 2 * K || coef.numel() < 3 * (int64_t)K ||
-      b.numel() < C || b.scalar_type() != at::kFloat || coef.scalar_type() != at::kFloat)
+  if (C < 1 || K < 1 || wT.numel() < (int64_t)C * K || w2.numel() < (int64_t)C * 2 * K ||
+      coef.numel() < 3 * (int64_t)K || b.numel() < C || b.scalar_type() != at::kFloat ||
+      coef.scalar_type() != at::kFloat)
     throw std::runtime_error("dual_dgrad_weights: shapes / dtypes");
   check(dlmpi_dual_dgrad_weights(wT.data_ptr(), C, K, ptr<float>(coef), w2.data_ptr(), ptr<float>(b),
                                  act_f32(wT, "dual_dgrad_weights"), cur_stream()),
@@ -111,6 +220,9 @@ void dual_dgrad_weights(const at::Tensor& wT, int C, int K, const at::Tensor& co
 }
 
 void channel_sum(const at::Tensor& x, int64_t M, int C, int ldx, int xoff, at::Tensor out_acc) {
+  rowmap_shape(M, C, "channel_sum");
+  slice_ok(x, M, C, ldx, xoff, "channel_sum", "x");
+  floats_ok(out_acc, C, "channel_sum", "out_acc");
   const int nblk = dlmpi_reduce_blocks(M, C);
   at::Tensor partial = at::empty({(int64_t)nblk * 2 * C}, x.options().dtype(at::kFloat));
   at::Tensor ws = colsum_ws(partial, nblk, C);
@@ -145,6 +257,8 @@ void maxpool_bwd(const at::Tensor& dy, const at::Tensor& idx, int N, int H, int 
 at::Tensor outer_dgrad_bn(const at::Tensor& dy, int lddy, int64_t M, int C, const at::Tensor& w, int ldw,
                           const at::Tensor& z, const at::Tensor& mscale, const at::Tensor& mshift, at::Tensor dx) {
   require_gpu(dy, "dy");
+  if (C < 8 || C % 8 || C > 2048 || M < 1)
+    throw std::runtime_error("outer_dgrad_bn: C a multiple of 8 in [8, 2048], M >= 1");
   const int64_t rpb = 256 / (C / 8);
   const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (M + rpb * 8 - 1) / (rpb * 8)));
   at::Tensor part = at::empty({nblk, 2, C}, dy.options().dtype(at::kFloat));
@@ -189,6 +303,7 @@ at::Tensor maxpool_bwd_bn(const at::Tensor& dy, const at::Tensor& idx, int N, in
                           const at::Tensor& mshift, const c10::optional<at::Tensor>& add, int ldadd, int addoff,
                           at::Tensor dx) {
   // more blocks than the generic reductions: every row is a latency-bound window gather
+  if (C < 8 || C % 8 || C > 2048) throw std::runtime_error("maxpool_bwd_bn: C a multiple of 8 in [8, 2048]");
   const int64_t rpb = 256 / (C / 8);
   const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(4096, ((int64_t)N * H * W + rpb * 8 - 1) / (rpb * 8)));
   at::Tensor part = at::empty({nblk, 2, C}, dy.options().dtype(at::kFloat));

@@ -640,7 +640,9 @@ static inline unsigned ew_blocks(int64_t total) {
 
 using namespace dlmpi;
 
+// 0: the row map (rowmap: 256 / (C / 8) row lanes) does not exist for this C, or there are no rows
 extern "C" int dlmpi_reduce_blocks(int64_t M, int C) {
+  if (C < 8 || C % 8 || C > 2048 || M < 1) return 0;
   const int CC = C / 8;
   const int rpb = 256 / CC;
   int64_t b = (M + (int64_t)rpb * 16 - 1) / ((int64_t)rpb * 16);
@@ -666,7 +668,7 @@ extern "C" int dlmpi_reduce_blocks(int64_t M, int C) {
 
 extern "C" hipError_t dlmpi_bn_stats(const void* x, int64_t M, int C, int ldx, int xoff, float* partial, int nblk,
                                      int f32, hipStream_t s) {
-  if (C % 8 || C > 2048) return hipErrorInvalidValue;
+  if (C < 8 || C % 8 || C > 2048 || M < 1 || nblk < 1) return hipErrorInvalidValue;
   LAUNCH_TLAUNCH(bn_stats_kernel, dim3(nblk), CT(x), M, C, ldx, xoff, partial);
   return hipGetLastError();
 }
@@ -856,7 +858,7 @@ extern "C" hipError_t dlmpi_bn_bwd_reduce(const void* dy, int lddy, int dyoff, c
                                           int ymoff, const void* x, int ldx, int xoff, int64_t M, int C,
                                           const float* mean, const float* invstd, float* partial, int nblk,
                                           int f32, hipStream_t s) {
-  if (C % 8 || C > 2048) return hipErrorInvalidValue;
+  if (C < 8 || C % 8 || C > 2048 || M < 1 || nblk < 1 || (x && !(mean && invstd))) return hipErrorInvalidValue;
   LAUNCH_TLAUNCH(bn_bwd_reduce_kernel, dim3(nblk), CT(dy), lddy, dyoff, CT(ymask), ldym, ymoff, CT(x), ldx, xoff, M, C,
                 mean, invstd, partial);
   return hipGetLastError();
