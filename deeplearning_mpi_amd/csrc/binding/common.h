@@ -47,6 +47,18 @@ static inline void same_type(const at::Tensor& ref, const at::Tensor& t, const c
   same_type(ref, c10::optional<at::Tensor>(t), what);
 }
 
+// The facts of a tensor argument the argument checks (conv_plan.h) work on; absent: numel -1.
+static inline int64_t onumel(const c10::optional<at::Tensor>& t) {
+  return (t.has_value() && t->defined()) ? (int64_t)t->numel() : -1;
+}
+static inline Operand operand(const at::Tensor& t, int ld, int off) { return Operand{(int64_t)t.numel(), ld, off}; }
+static inline Operand operand(const c10::optional<at::Tensor>& t, int ld, int off) {
+  return Operand{onumel(t), ld, off};
+}
+static inline void require_ok(const std::string& err) {
+  if (!err.empty()) throw std::runtime_error(err);
+}
+
 static inline at::Tensor colsum_ws(const at::Tensor& like, int T, int C) {
   return at::empty({(int64_t)dlmpi_colsum_ws_doubles(T, C)}, like.options().dtype(at::kDouble));
 }

@@ -35,9 +35,19 @@ c10::optional<at::Tensor> conv2d_dgrad_pro(const at::Tensor& dy, int N, int P, i
                                        const c10::optional<at::Tensor>& pz, int ldpz, int pzoff,
                                        const c10::optional<at::Tensor>& bias) {
   require_gpu(dy, "dy");
-  if (stride > 2) throw std::runtime_error("conv2d_dgrad: stride <= 2 supported");
-  if (bias.has_value() && bias->defined() && (bias->scalar_type() != at::kFloat || bias->numel() < C))
-    throw std::runtime_error("conv2d_dgrad: bias must be fp32 [C]");
+  {
+    DgradCheck c{N, P, Q, K, C, R, S, stride, pad, H, W, operand(dy, lddy, dyoff), operand(dx, lddx, dxoff),
+                 operand(res, ldres, resoff), operand(mask, ldmask, maskoff), operand(z, ldz, zoff),
+                 operand(z2, ldz2, z2off), (int64_t)wT.numel()};
+    c.bias_numel = onumel(bias);
+    c.mscale_numel = onumel(mscale);
+    c.mshift_numel = onumel(mshift);
+    c.mbits_numel = onumel(mbits);
+    c.colsum = colsum;
+    require_ok(check_dgrad_args(c));
+  }
+  if (bias.has_value() && bias->defined() && bias->scalar_type() != at::kFloat)
+    throw std::runtime_error("conv2d_dgrad: bias must be fp32");
   ConvArgs a{};
   a.f32 = act_f32(dy, "conv2d_dgrad");
   same_type(dy, wT, "conv2d_dgrad wT");
@@ -65,8 +75,6 @@ c10::optional<at::Tensor> conv2d_dgrad_pro(const at::Tensor& dy, int N, int P, i
   a.mscale = optr<float>(mscale);
   a.mshift = optr<float>(mshift);
   a.mbits = optr<uint8_t>(mbits);
-  if (a.mbits && (mbits->numel() != (int64_t)N * H * W * (C / 8) || C % 8))
-    throw std::runtime_error("conv2d_dgrad: mask bits must be [N*H*W][C/8]");
   a.nstat = a.z2 ? 3 : 2;
   if (a.z && !a.mask && !a.mscale && !a.mbits)
     throw std::runtime_error("conv2d_dgrad: fused BN statistics need the ReLU mask");
@@ -184,7 +192,8 @@ c10::optional<at::Tensor> conv2d_dgrad_pro(const at::Tensor& dy, int N, int P, i
   c10::optional<at::Tensor> stats;
   if (a.z || colsum) {
     // colsum without BN fusion: per-tile {sum dx, sum dx^2} of the stored gradient (UNet: the
-    // column sums of the up-sampling slice are the ConvTranspose2d bias gradient)
+    // column sums of the up-sampling slice are the ConvTranspose2d bias gradient).  The epilogue takes
+    // them before it would add a residual, so check_dgrad_args refuses colsum together with res.
     stats = at::empty({(int64_t)tiles, (int64_t)a.nstat, (int64_t)C}, dy.options().dtype(at::kFloat));
     a.stats = ptr<float>(*stats);
   }
@@ -312,6 +321,9 @@ void conv2d_wgrad_pro(const at::Tensor& dy, int lddy, int dyoff, int Ko, const a
                       const c10::optional<at::Tensor>& pz, int ldpz, int pzoff, int pro_b,
                       const c10::optional<at::Tensor>& pscale, const c10::optional<at::Tensor>& pshift) {
   require_gpu(dy, "dy");
+  require_ok(check_wgrad_args(WgradCheck{N, H, W, C, Ko, R, S, stride, pad, P, Q, Creal, Ko_real, operand(dy, lddy, dyoff),
+                                         operand(x, ldx, xoff), (int64_t)grad.numel()}));
+  if (grad.scalar_type() != at::kFloat) throw std::runtime_error("conv2d_wgrad: the gradient must be fp32");
   if (C % 8 != 0 || Ko % 8 != 0) throw std::runtime_error("conv2d_wgrad: channels must be multiples of 8");
   WgradArgs a{};
   a.f32 = act_f32(dy, "conv2d_wgrad");
@@ -435,6 +447,45 @@ void register_conv_bwd(pybind11::module& m) {
   m.def("conv2d_dgrad_pro", &conv2d_dgrad_pro);
   m.def("conv2d_wgrad", &conv2d_wgrad);
   m.def("conv2d_wgrad_pro", &conv2d_wgrad_pro);
+  // check_dgrad_args / check_wgrad_args on plain integers (tests, no GPU): "" or the refusal the entry
+  // point would throw.  Element counts of absent operands: -1.
+  namespace py = pybind11;
+  m.def(
+      "conv2d_dgrad_check",
+      [](int N, int P, int Q, int K, int C, int R, int S, int stride, int pad, int H, int W, int64_t dy_numel, int lddy,
+         int dyoff, int64_t wT_numel, int64_t dx_numel, int lddx, int dxoff, int64_t res_numel, int ldres, int resoff,
+         int64_t mask_numel, int ldmask, int maskoff, int64_t z_numel, int ldz, int zoff, int64_t z2_numel, int ldz2,
+         int z2off, int64_t mscale_numel, int64_t mshift_numel, int64_t mbits_numel, int64_t bias_numel, bool colsum) {
+        DgradCheck c{N, P, Q, K, C, R, S, stride, pad, H, W, Operand{dy_numel, lddy, dyoff},
+                     Operand{dx_numel, lddx, dxoff}, Operand{res_numel, ldres, resoff},
+                     Operand{mask_numel, ldmask, maskoff}, Operand{z_numel, ldz, zoff}, Operand{z2_numel, ldz2, z2off},
+                     wT_numel};
+        c.bias_numel = bias_numel;
+        c.mscale_numel = mscale_numel;
+        c.mshift_numel = mshift_numel;
+        c.mbits_numel = mbits_numel;
+        c.colsum = colsum;
+        return check_dgrad_args(c);
+      },
+      py::arg("N"), py::arg("P"), py::arg("Q"), py::arg("K"), py::arg("C"), py::arg("R"), py::arg("S"),
+      py::arg("stride"), py::arg("pad"), py::arg("H"), py::arg("W"), py::arg("dy_numel"), py::arg("lddy"),
+      py::arg("dyoff"), py::arg("wT_numel"), py::arg("dx_numel"), py::arg("lddx"), py::arg("dxoff"),
+      py::arg("res_numel") = -1, py::arg("ldres") = 0, py::arg("resoff") = 0, py::arg("mask_numel") = -1,
+      py::arg("ldmask") = 0, py::arg("maskoff") = 0, py::arg("z_numel") = -1, py::arg("ldz") = 0, py::arg("zoff") = 0,
+      py::arg("z2_numel") = -1, py::arg("ldz2") = 0, py::arg("z2off") = 0, py::arg("mscale_numel") = -1,
+      py::arg("mshift_numel") = -1, py::arg("mbits_numel") = -1, py::arg("bias_numel") = -1,
+      py::arg("colsum") = false);
+  m.def(
+      "conv2d_wgrad_check",
+      [](int N, int H, int W, int C, int Ko, int R, int S, int stride, int pad, int P, int Q, int Creal, int Ko_real,
+         int64_t dy_numel, int lddy, int dyoff, int64_t x_numel, int ldx, int xoff, int64_t grad_numel) {
+        return check_wgrad_args(WgradCheck{N, H, W, C, Ko, R, S, stride, pad, P, Q, Creal, Ko_real,
+                                           Operand{dy_numel, lddy, dyoff}, Operand{x_numel, ldx, xoff}, grad_numel});
+      },
+      py::arg("N"), py::arg("H"), py::arg("W"), py::arg("C"), py::arg("Ko"), py::arg("R"), py::arg("S"),
+      py::arg("stride"), py::arg("pad"), py::arg("P"), py::arg("Q"), py::arg("Creal"), py::arg("Ko_real"),
+      py::arg("dy_numel"), py::arg("lddy"), py::arg("dyoff"), py::arg("x_numel"), py::arg("ldx"), py::arg("xoff"),
+      py::arg("grad_numel"));
   m.def("set_wgrad_defer", [](bool on) {
     if (!on) wgrad_flush();
     g_wgrad_defer = on;

@@ -301,6 +301,25 @@ static void run_fin_after(const at::Tensor& stats, int rows, int K, const FinArg
         "bn_finalize");
 }
 
+// the sizes of a forward call, for check_fwd_args (conv_plan.h)
+static FwdCheck fwd_check(const at::Tensor& x, int N, int H, int W, int C, int ldx, int xoff, const at::Tensor& w, int K,
+                          int R, int S, int stride, int pad, const at::Tensor& y, int ldy, int yoff,
+                          const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& res, int ldres,
+                          int resoff, const c10::optional<at::Tensor>& scale, const c10::optional<at::Tensor>& shift,
+                          const c10::optional<at::Tensor>& stats, int kvalid) {
+  FwdCheck c{N, H, W, C, K, R, S, stride, pad, kvalid, operand(x, ldx, xoff), operand(y, ldy, yoff),
+             operand(res, ldres, resoff), (int64_t)w.numel()};
+  c.bias_numel = onumel(bias);
+  c.scale_numel = onumel(scale);
+  c.shift_numel = onumel(shift);
+  if (stats.has_value() && stats->defined()) {
+    c.stats_rows = stats->dim() > 0 ? stats->size(0) : 0;
+    c.stats_cols = c.stats_rows > 0 ? stats->numel() / c.stats_rows : 0;
+    c.stats_f32 = stats->scalar_type() == at::kFloat;
+  }
+  return c;
+}
+
 // y[n, p, q, yoff + k] = epilogue( sum_{r,s,c} x[n, p*stride - pad + r, q*stride - pad + s, xoff + c] * w[k][r][s][c] )
 // fin (with stats): also finalize the BatchNorm over these statistics, by the standalone finalize
 // right after the launch.  Returns the rows of the stats partial buffer the launch wrote.
@@ -312,6 +331,8 @@ static int conv2d_fwd_impl(const at::Tensor& x, int N, int H, int W, int C, int 
                const c10::optional<at::Tensor>& pk1, const c10::optional<at::Tensor>& pz, int ldpz, int pzoff,
                const FinArgs* fin) {
   require_gpu(x, "x");
+  require_ok(check_fwd_args(fwd_check(x, N, H, W, C, ldx, xoff, w, K, R, S, stride, pad, y, ldy, yoff, bias, res, ldres,
+                                      resoff, scale, shift, stats, kvalid)));
   const ConvShape s{N, H, W, C, K, R, S, stride, pad, pro, act_f32(x, "conv2d_fwd"), bm_req, bn_req};
   const int P = s.P(), Q = s.Q();
   same_type(x, w, "conv2d_fwd w");
@@ -470,6 +491,8 @@ int conv3x3_fwd_bn_apply(const at::Tensor& x, int N, int H, int W, int ldx, int 
       !conv3_pro_ok(N, H, W, 64, 64, ldx, xoff, ldz, zoff, ldyapp, yappoff) || ascale.numel() < 64 ||
       ashift.numel() < 64)
     return -1;
+  require_ok(check_fwd_args(fwd_check(x, N, H, W, 64, ldx, xoff, w, 64, 3, 3, 1, 1, z, ldz, zoff, bias, yapp, ldyapp,
+                                      yappoff, c10::nullopt, c10::nullopt, stats, 0)));   // yapp: N*H*W x 64, like a residual
   int th, tw, G;
   stream3x3_shape(N, H, W, 64, 64, 3, 3, 1, 1, 0, 0, th, tw, G);
   if (stats.size(0) < G) throw std::runtime_error("conv3x3_fwd_bn_apply: stats buffer too small");
@@ -516,6 +539,11 @@ at::Tensor conv2d_fwd_bnbwd(const at::Tensor& x, int N, int H, int W, int C, int
                             const at::Tensor& z, int ldz, int zoff, const at::Tensor& mscale,
                             const at::Tensor& mshift) {
   require_gpu(x, "x");
+  {
+    FwdCheck c = fwd_check(x, N, H, W, C, ldx, xoff, w, K, R, S, stride, pad, y, ldy, yoff, c10::nullopt, z, ldz, zoff,
+                           mscale, mshift, c10::nullopt, 0);   // z: an N*P*Q x K operand like a residual
+    require_ok(check_fwd_args(c));
+  }
   const ConvShape s{N, H, W, C, K, R, S, stride, pad, 0, act_f32(x, "conv2d_fwd_bnbwd"), 0, 0};
   same_type(x, w, "conv2d_fwd_bnbwd w");
   same_type(x, z, "conv2d_fwd_bnbwd z");
@@ -628,6 +656,30 @@ void register_conv_fwd(pybind11::module& m) {
   m.def("conv2d_fwd_mtiles", &conv2d_fwd_mtiles);
   m.def("conv2d_fwd_mtiles_pro", &conv2d_fwd_mtiles_pro);
   m.def("conv2d_fwd_plan", &conv2d_fwd_plan);
+  // check_fwd_args on plain integers (tests, no GPU): "" or the refusal conv2d_fwd* would throw.
+  // Element counts of absent operands: -1.
+  m.def(
+      "conv2d_fwd_check",
+      [](int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int kvalid, int64_t x_numel, int ldx,
+         int xoff, int64_t w_numel, int64_t y_numel, int ldy, int yoff, int64_t bias_numel, int64_t res_numel, int ldres,
+         int resoff, int64_t scale_numel, int64_t shift_numel, int64_t stats_rows, int64_t stats_cols, bool stats_f32) {
+        FwdCheck c{N, H, W, C, K, R, S, stride, pad, kvalid, Operand{x_numel, ldx, xoff}, Operand{y_numel, ldy, yoff},
+                   Operand{res_numel, ldres, resoff}, w_numel};
+        c.bias_numel = bias_numel;
+        c.scale_numel = scale_numel;
+        c.shift_numel = shift_numel;
+        c.stats_rows = stats_rows;
+        c.stats_cols = stats_cols;
+        c.stats_f32 = stats_f32;
+        return check_fwd_args(c);
+      },
+      pybind11::arg("N"), pybind11::arg("H"), pybind11::arg("W"), pybind11::arg("C"), pybind11::arg("K"),
+      pybind11::arg("R"), pybind11::arg("S"), pybind11::arg("stride"), pybind11::arg("pad"),
+      pybind11::arg("kvalid") = 0, pybind11::arg("x_numel"), pybind11::arg("ldx"), pybind11::arg("xoff"),
+      pybind11::arg("w_numel"), pybind11::arg("y_numel"), pybind11::arg("ldy"), pybind11::arg("yoff"),
+      pybind11::arg("bias_numel") = -1, pybind11::arg("res_numel") = -1, pybind11::arg("ldres") = 0,
+      pybind11::arg("resoff") = 0, pybind11::arg("scale_numel") = -1, pybind11::arg("shift_numel") = -1,
+      pybind11::arg("stats_rows") = -1, pybind11::arg("stats_cols") = 0, pybind11::arg("stats_f32") = true);
   m.def("conv_tune_tiles", [](int f32, int C, int K) {
     std::vector<std::pair<int, int>> v;
     for (const TuneCand& c : tune_candidates(f32, C, K, 0)) v.emplace_back(c.bm, c.bn);

@@ -365,6 +365,124 @@ int fwd_rows_bound(const ConvShape& s) {
   return rows;
 }
 
+// ---- argument checks (conv_plan.h) ----------------------------------------------------------------
+namespace {
+struct Checker {
+  std::string err;
+  bool ok() const { return err.empty(); }
+  void fail(const std::string& m) {
+    if (err.empty()) err = m;
+  }
+  void positive(const char* name, int64_t v) {
+    if (v <= 0) fail(std::string(name) + " must be positive (got " + std::to_string(v) + ")");
+  }
+  // the extent rule of conv_plan.h
+  void operand(const char* name, const Operand& o, int64_t rows, int width) {
+    if (!ok() || !o.given()) return;
+    if (o.off < 0 || o.ld <= 0 || (int64_t)o.off + width > o.ld)
+      return fail(std::string(name) + ": channel slice [" + std::to_string(o.off) + ", " +
+                  std::to_string((int64_t)o.off + width) + ") does not fit its row stride " + std::to_string(o.ld));
+    const int64_t need = (rows - 1) * o.ld + o.off + width;
+    if (o.numel < need)
+      fail(std::string(name) + ": buffer of " + std::to_string(o.numel) + " elements is shorter than the " +
+           std::to_string(need) + " the launch reaches (" + std::to_string(rows) + " rows of stride " +
+           std::to_string(o.ld) + ")");
+  }
+  void required(const char* name, const Operand& o) {
+    if (!o.given()) fail(std::string(name) + " is required");
+  }
+  void vec(const char* name, int64_t numel, int64_t need) {
+    if (ok() && numel >= 0 && numel < need)
+      fail(std::string(name) + ": " + std::to_string(numel) + " elements, " + std::to_string(need) + " needed");
+  }
+};
+// sizes and the output grid; returns P, Q of the geometry (0 when it is not even defined)
+void check_geometry(Checker& k, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int& P, int& Q) {
+  k.positive("N", N); k.positive("H", H); k.positive("W", W); k.positive("C", C); k.positive("K", K);
+  k.positive("R", R); k.positive("S", S); k.positive("stride", stride);
+  if (pad < 0) k.fail("pad must not be negative");
+  P = Q = 0;
+  if (!k.ok()) return;
+  if (H + 2 * pad < R || W + 2 * pad < S) return k.fail("the output grid is empty: the padded image is smaller than the kernel");
+  P = (H + 2 * pad - R) / stride + 1;
+  Q = (W + 2 * pad - S) / stride + 1;
+  if ((int64_t)N * H * W >= (1ll << 31) || (int64_t)N * P * Q >= (1ll << 31)) k.fail("more than 2^31 - 1 pixels");
+}
+}  // namespace
+
+std::string check_fwd_args(const FwdCheck& c) {
+  Checker k;
+  int P, Q;
+  check_geometry(k, c.N, c.H, c.W, c.C, c.K, c.R, c.S, c.stride, c.pad, P, Q);
+  if (!k.ok()) return "conv2d_fwd: " + k.err;
+  const int64_t Min = (int64_t)c.N * c.H * c.W, M = (int64_t)c.N * P * Q;
+  const int stored = c.kvalid > 0 && c.kvalid < c.K ? c.kvalid : c.K;
+  k.required("x", c.x);
+  k.required("y", c.y);
+  k.operand("x", c.x, Min, c.C);
+  k.operand("y", c.y, M, stored);
+  k.operand("res", c.res, M, c.K);
+  k.vec("w", c.w_numel < 0 ? 0 : c.w_numel, (int64_t)c.K * c.R * c.S * c.C);
+  k.vec("bias", c.bias_numel, c.K);
+  k.vec("scale", c.scale_numel, c.K);
+  k.vec("shift", c.shift_numel, c.K);
+  if ((c.scale_numel >= 0) != (c.shift_numel >= 0)) k.fail("scale and shift come together");
+  if (c.stats_rows >= 0) {
+    if (!c.stats_f32) k.fail("stats must be fp32");
+    if (c.stats_rows == 0 || c.stats_cols != 2 * (int64_t)c.K)
+      k.fail("stats must be [rows][2*K]: " + std::to_string(c.stats_cols) + " columns for K = " + std::to_string(c.K));
+  }
+  return k.ok() ? "" : "conv2d_fwd: " + k.err;
+}
+
+std::string check_dgrad_args(const DgradCheck& c) {
+  Checker k;
+  int P, Q;
+  check_geometry(k, c.N, c.H, c.W, c.C, c.K, c.R, c.S, c.stride, c.pad, P, Q);
+  if (k.ok() && c.stride > 2) k.fail("stride <= 2 supported");
+  if (k.ok() && (c.P != P || c.Q != Q))
+    k.fail("dy grid " + std::to_string(c.P) + " x " + std::to_string(c.Q) + " is not the " + std::to_string(P) + " x " +
+           std::to_string(Q) + " output of this conv on a " + std::to_string(c.H) + " x " + std::to_string(c.W) + " input");
+  if (!k.ok()) return "conv2d_dgrad: " + k.err;
+  const int64_t Min = (int64_t)c.N * c.H * c.W, M = (int64_t)c.N * P * Q;
+  k.required("dy", c.dy);
+  k.required("dx", c.dx);
+  k.operand("dy", c.dy, M, c.K);
+  k.operand("dx", c.dx, Min, c.C);
+  k.operand("res", c.res, Min, c.C);
+  k.operand("mask", c.mask, Min, c.C);
+  k.operand("z", c.z, Min, c.C);
+  k.operand("z2", c.z2, Min, c.C);
+  k.vec("wT", c.wT_numel < 0 ? 0 : c.wT_numel, (int64_t)c.C * c.R * c.S * c.K);
+  k.vec("bias", c.bias_numel, c.C);
+  k.vec("mscale", c.mscale_numel, c.C);
+  k.vec("mshift", c.mshift_numel, c.C);
+  if (c.mbits_numel >= 0 && (c.C % 8 || c.mbits_numel != Min * (c.C / 8))) k.fail("mask bits must be [N*H*W][C/8]");
+  // conv_epilogue takes the unmasked column sums before it adds the residual: they would not be the
+  // sums of the stored dx
+  if (c.colsum && c.res.given() && !c.mask.given() && c.mscale_numel < 0 && c.mbits_numel < 0)
+    k.fail("colsum with a residual is not built (the column sums are taken before the residual is added)");
+  return k.ok() ? "" : "conv2d_dgrad: " + k.err;
+}
+
+std::string check_wgrad_args(const WgradCheck& c) {
+  Checker k;
+  int P, Q;
+  check_geometry(k, c.N, c.H, c.W, c.C, c.Ko, c.R, c.S, c.stride, c.pad, P, Q);
+  if (k.ok() && (c.P != P || c.Q != Q))
+    k.fail("dy grid " + std::to_string(c.P) + " x " + std::to_string(c.Q) + " is not the " + std::to_string(P) + " x " +
+           std::to_string(Q) + " output of this conv on a " + std::to_string(c.H) + " x " + std::to_string(c.W) + " input");
+  if (k.ok() && (c.Creal < 0 || c.Creal > c.C || c.Ko_real < 0 || c.Ko_real > c.Ko))
+    k.fail("Creal / Ko_real must lie in [0, C] / [0, Ko]");
+  if (!k.ok()) return "conv2d_wgrad: " + k.err;
+  k.required("dy", c.dy);
+  k.required("x", c.x);
+  k.operand("dy", c.dy, (int64_t)c.N * P * Q, c.Ko);
+  k.operand("x", c.x, (int64_t)c.N * c.H * c.W, c.C);
+  k.vec("grad", c.grad_numel < 0 ? 0 : c.grad_numel, (int64_t)c.Ko_real * c.R * c.S * c.Creal);
+  return k.ok() ? "" : "conv2d_wgrad: " + k.err;
+}
+
 // The streaming 64 -> 64 3x3 forward takes this launch with the producer's BN-apply + ReLU fused
 // (conv3x3_stream_kernel PRO): shape and operand conditions (the model asks before it defers the apply).
 // The kernel addresses 64-channel rows of x and of the applied output from their offsets.

@@ -4,6 +4,7 @@
 // rules the launch follows (plan_fwd), and both can be exercised without a GPU.
 #pragma once
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "../kernels/dlmpi_kernels.h"
@@ -112,6 +113,47 @@ std::vector<TuneCand> tune_candidates(int f32, int C, int Kout, int maxk);
 FwdPlan plan_fwd(const ConvShape& s, const FwdOperands& o);
 // Upper bound of plan_fwd(s, any operands).rows -- and of an autotuned launch's: the caller's buffer.
 int fwd_rows_bound(const ConvShape& s);
+
+// ---- argument checks of the conv entry points ----------------------------------------------------
+// Pure integer arithmetic over sizes and element counts, run by conv2d_fwd* / conv2d_dgrad* /
+// conv2d_wgrad* before anything is launched (and by the conv2d_*_check bindings without a GPU).
+// Each returns "" for a valid call, else what is wrong.
+//
+// An operand is a channel slice [off, off + width) of the rows of an [rows][ld] buffer of `numel`
+// elements.  THE EXTENT RULE: the last element the launch may touch lies inside the buffer,
+//   (rows - 1) * ld + off + width <= numel,  with off >= 0 and off + width <= ld
+// (not rows * ld: a slice of a wider allocation may end with its last row).  numel < 0: operand absent.
+struct Operand {
+  int64_t numel = -1;
+  int ld = 0, off = 0;
+  bool given() const { return numel >= 0; }
+};
+struct FwdCheck {
+  int N, H, W, C, K, R, S, stride, pad;
+  int kvalid;                    // <= 0 or >= K: all K channels are stored
+  Operand x, y, res;             // x: N*H*W rows of C; y: N*P*Q rows of the stored channels; res: N*P*Q rows of K
+  int64_t w_numel;               // >= K*R*S*C
+  int64_t bias_numel = -1, scale_numel = -1, shift_numel = -1;   // per-channel vectors: >= K
+  int64_t stats_rows = -1, stats_cols = 0;                      // statistics [rows][2*K] ...
+  bool stats_f32 = true;                                         // ... in fp32
+};
+struct DgradCheck {
+  int N, P, Q, K, C, R, S, stride, pad, H, W;
+  Operand dy, dx, res, mask, z, z2;   // dy: N*P*Q rows of K; the others N*H*W rows of C
+  int64_t wT_numel;                   // >= C*R*S*K
+  int64_t bias_numel = -1, mscale_numel = -1, mshift_numel = -1;   // >= C
+  int64_t mbits_numel = -1;           // == N*H*W * C/8
+  bool colsum = false;                // column sums without a mask: not together with res (taken before it is added)
+};
+struct WgradCheck {
+  int N, H, W, C, Ko, R, S, stride, pad, P, Q;
+  int Creal, Ko_real;            // 0 <= Creal <= C, 0 <= Ko_real <= Ko: the packed gradient [Ko_real][R*S][Creal]
+  Operand dy, x;                 // dy: N*P*Q rows of Ko; x: N*H*W rows of C
+  int64_t grad_numel;            // >= Ko_real * R*S * Creal
+};
+std::string check_fwd_args(const FwdCheck& c);
+std::string check_dgrad_args(const DgradCheck& c);
+std::string check_wgrad_args(const WgradCheck& c);
 
 bool stream3x3_shape(int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int pro, int f32, int& th,
                      int& tw, int& G);
