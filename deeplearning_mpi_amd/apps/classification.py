@@ -4,7 +4,7 @@ Flags keep the reference names and defaults: --num_epochs, --b
 process), --learning_rate, --random_seed, --model_dir, --model_filename, --resume.  Non-breaking
 additions: --arch, --num_classes, --synthetic, --data_root, --image_size, --backend, --device,
 --bucket_mb, --workers, --eval_every, --steps_per_epoch, --precision, --graph, --data_on_device,
---benchmark_steps.
+--benchmark_steps, --label_smoothing, --mixup_alpha, --cutmix_alpha, --mix_prob, --mix_switch_prob.
 
 Deliberate fixes of reference quirks (SURVEY.md §7.3): the sampler's epoch is advanced every epoch;
 evaluation runs on the unwrapped module (no stray rank-0-only collective, K8) with a non-augmenting
@@ -14,6 +14,7 @@ device (one host sync per epoch instead of one per step).
 from __future__ import annotations
 
 import argparse
+import math
 import os
 import random
 import time
@@ -23,7 +24,8 @@ import torch
 from torch.utils.data import DataLoader
 
 from .. import parallel
-from ..data import CIFAR10, CifarTransform, DeviceBatches, DeviceImageDataset, DistributedSampler, SyntheticImages
+from ..data import (CIFAR10, CifarTransform, DeviceBatches, DeviceImageDataset, DistributedSampler, MixConfig,
+                    SyntheticImages, draw_mix, mix_batch_)
 from ..models import ARCHS
 from ..ops import CrossEntropyLoss, backward, top1_correct
 from ..optim import LARS, SGD
@@ -69,7 +71,37 @@ def build_argparser(variant: str = "main") -> argparse.ArgumentParser:
     p.add_argument("--benchmark_steps", type=int, default=0,
                    help="time this many steps on a synthetic device batch, print images/sec and exit")
     add_layerwise_args(p, "sgd", "lars")
+    add_recipe_args(p)
     return p
+
+
+def add_recipe_args(p):
+    """Label smoothing and mixup / CutMix (data/mix.py): the regularisers of the large-batch recipe."""
+    p.add_argument("--label_smoothing", type=float, default=0.0, help="label smoothing of the training loss, in [0, 1)")
+    p.add_argument("--mixup_alpha", type=float, default=0.0, help="mixup with lam ~ Beta(a, a) per batch (0 = off)")
+    p.add_argument("--cutmix_alpha", type=float, default=0.0, help="CutMix with lam ~ Beta(a, a) per batch (0 = off)")
+    p.add_argument("--mix_prob", type=float, default=1.0, help="probability that a batch is mixed at all")
+    p.add_argument("--mix_switch_prob", type=float, default=0.5,
+                   help="with both alphas > 0: probability that a mixed batch is CutMix rather than mixup")
+
+
+def check_recipe_args(parser, args):
+    if not (math.isfinite(args.label_smoothing) and 0 <= args.label_smoothing < 1):
+        parser.error("--label_smoothing must lie in [0, 1)")
+    for name in ("mixup_alpha", "cutmix_alpha"):
+        v = getattr(args, name)
+        if not (math.isfinite(v) and v >= 0):
+            parser.error(f"--{name} must be finite and >= 0")
+    for name in ("mix_prob", "mix_switch_prob"):
+        if not 0 <= getattr(args, name) <= 1:
+            parser.error(f"--{name} must lie in [0, 1]")
+
+
+def recipe_of(args):
+    """The mix configuration when any recipe flag is set, else None (then the step is built as without them)."""
+    cfg = MixConfig(getattr(args, "mixup_alpha", 0.0), getattr(args, "cutmix_alpha", 0.0),
+                    getattr(args, "mix_prob", 1.0), getattr(args, "mix_switch_prob", 0.5))
+    return cfg if (getattr(args, "label_smoothing", 0.0) > 0 or cfg.enabled) else None
 
 
 def add_layerwise_args(p, plain: str, layerwise: str):
@@ -154,6 +186,10 @@ def run(args) -> dict:
     x_static = torch.empty((args.batch_size, 3, args.image_size, args.image_size) if args.synthetic else
                            (args.batch_size, 3, 32, 32), device=device)
     y_static = torch.zeros(args.batch_size, dtype=torch.int64, device=device)
+    static = (x_static, y_static)
+    mix_cfg = recipe_of(args)
+    if mix_cfg is not None:   # the step reads a mixed target: (x, labels_a, labels_b, lam), all on the device
+        static += (torch.zeros_like(y_static), torch.ones(1, dtype=torch.float32, device=device))
     on_device = (args.data_on_device == "1" or
                  (args.data_on_device == "auto" and device.type == "cuda" and not args.synthetic))
     test_bs = args.test_batch_size or args.batch_size
@@ -163,7 +199,7 @@ def run(args) -> dict:
         test_set = SyntheticImages(max(64, args.synthetic_size // 8), shape, args.num_classes, seed=2)
     elif on_device:
         # the whole dataset in HBM; one kernel per batch does gather + crop/flip + normalize
-        train_set = DeviceImageDataset.cifar10(args.data_root, True, device, seed=args.random_seed)
+        train_set = DeviceImageDataset.cifar10(args.data_root, True, device, seed=args.random_seed, mix=mix_cfg)
         test_set = DeviceImageDataset.cifar10(args.data_root, False, device, augment=False)
     else:
         # download=False semantics: the data must already be under data_root (see download.py)
@@ -174,7 +210,7 @@ def run(args) -> dict:
     sampler = DistributedSampler(train_set, seed=0)
     if on_device and not args.synthetic:
         train_loader = DeviceBatches(train_set, args.batch_size, sampler,
-                                     out=(x_static, y_static) if args.graph else None)
+                                     out=static if args.graph else None)
         test_loader = DeviceBatches(test_set, test_bs)
     else:
         pin = device.type == "cuda"
@@ -185,7 +221,7 @@ def run(args) -> dict:
         # state is the resume state every rank restores)
         test_loader = DataLoader(test_set, batch_size=test_bs, shuffle=False, num_workers=args.workers,
                                  pin_memory=pin, generator=torch.Generator().manual_seed(args.random_seed))
-    criterion = CrossEntropyLoss()
+    criterion = CrossEntropyLoss(label_smoothing=getattr(args, "label_smoothing", 0.0))
     if getattr(args, "optimizer", "sgd") == "lars":
         steps = args.benchmark_steps or args.num_epochs * (args.steps_per_epoch or len(train_loader))
         optimizer = LARS(model.parameters(), lr=args.learning_rate, momentum=0.9, weight_decay=1e-5,
@@ -199,20 +235,33 @@ def run(args) -> dict:
         start_epoch = int(meta.get("next_epoch", 0))
         set_rng_state(meta.get("rng"))
 
-    def train_step(x, y):
+    def train_step(x, y, y_b=None, lam=None):
         optimizer.zero_grad()
-        loss = criterion(ddp(x), y)
+        loss = criterion(ddp(x), y) if y_b is None else criterion(ddp(x), y, y_b, lam)
         backward(loss)
         optimizer.step()
         return loss
 
     captured = None
     if args.graph and device.type == "cuda":
-        captured = CapturedStep(lambda: train_step(x_static, y_static), warmup=2, inputs=(x_static, y_static),
-                                comm=comm)
+        captured = CapturedStep(lambda: train_step(*static), warmup=2, inputs=static, comm=comm)
 
     if args.benchmark_steps:
-        return benchmark(args, train_step, captured, x_static, y_static, comm, device)
+        return benchmark(args, train_step, captured, static, comm, device, mix_cfg)
+
+    def step_inputs(batch, epoch, batch_no):
+        """The batch on the device as the step takes it.  With the recipe flags a batch that the loader has not
+        mixed already (DataLoader, synthetic) is mixed in place here, outside the captured step -- a full batch
+        inside the step's fixed tensors."""
+        batch = tuple(t.to(device, non_blocking=True) for t in batch)
+        if mix_cfg is None or len(batch) == 4:
+            return batch
+        x, y = batch
+        p = draw_mix(mix_cfg, args.random_seed, epoch, rank, batch_no, x.shape[2], x.shape[3])
+        if captured is not None and x.shape[0] == args.batch_size:
+            captured.set_inputs(x, y)
+            return mix_batch_(static[0], static[1], p, static[2], static[3])
+        return mix_batch_(x.contiguous(), y, p)
 
     history = {"loss": [], "accuracy": [], "images_per_sec": []}
 
@@ -237,14 +286,13 @@ def run(args) -> dict:
             loss_sum = torch.zeros((), device=device)
             nb = 0
             t0 = time.perf_counter()
-            for inputs, labels in train_loader:
-                inputs = inputs.to(device, non_blocking=True)
-                labels = labels.to(device, non_blocking=True)
-                if captured is not None and inputs.shape[0] == args.batch_size:
-                    captured.set_inputs(inputs, labels)
+            for batch in train_loader:
+                batch = step_inputs(batch, epoch, nb)
+                if captured is not None and batch[0].shape[0] == args.batch_size:
+                    captured.set_inputs(*batch)
                     loss = captured()
                 else:   # eager step (also the ragged last batch of a graph run)
-                    loss = train_step(inputs, labels)
+                    loss = train_step(*batch)
                 loss_sum += loss.detach()
                 nb += 1
                 if args.steps_per_epoch and nb >= args.steps_per_epoch:
@@ -264,20 +312,29 @@ def run(args) -> dict:
     return history
 
 
-def benchmark(args, train_step, captured, x, y, comm, device) -> dict:
-    """--benchmark_steps: synthetic device batch, 3 warm-up steps, timed steps, images/sec."""
+def benchmark(args, train_step, captured, static, comm, device, mix_cfg=None) -> dict:
+    """--benchmark_steps: synthetic device batch, 3 warm-up steps, timed steps, images/sec.  With the recipe flags
+    a timed step is the in-place mix of the batch plus the training step."""
+    x, y = static[:2]
     g = torch.Generator(device=device).manual_seed(1234 + comm.rank)
     x.copy_(torch.randn(x.shape, generator=g, device=device))
     y.copy_(torch.randint(args.num_classes, y.shape, generator=g, device=device))
-    step = captured if captured is not None else (lambda: train_step(x, y))
-    for _ in range(3):
-        step()
+    run_step = captured if captured is not None else (lambda: train_step(*static))
+    if mix_cfg is None:
+        step = lambda i: run_step()   # noqa: E731
+    else:
+        def step(i):
+            p = draw_mix(mix_cfg, args.random_seed, 0, comm.rank, i, x.shape[2], x.shape[3])
+            mix_batch_(x, y, p, static[2], static[3])
+            return run_step()
+    for i in range(3):
+        step(i)
     comm.barrier()
     if device.type == "cuda":
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.benchmark_steps):
-        loss = step()
+    for i in range(args.benchmark_steps):
+        loss = step(3 + i)
     comm.barrier()
     if device.type == "cuda":
         torch.cuda.synchronize()
@@ -295,4 +352,5 @@ def main(variant="main", argv=None):
     parser = build_argparser(variant)
     args = parser.parse_args(argv)
     check_layerwise_args(parser, args, "sgd")
+    check_recipe_args(parser, args)
     return run(args)

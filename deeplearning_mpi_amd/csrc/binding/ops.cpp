@@ -408,6 +408,91 @@ static void f32_numel(const at::Tensor& t, int64_t n, const char* what) {
   if (t.scalar_type() != at::kFloat || !t.is_contiguous() || t.numel() != n || !t.is_cuda())
     throw std::runtime_error(std::string(what) + ": contiguous fp32 GPU tensor of " + std::to_string(n) + " elements");
 }
+// Classification cross-entropy with weight / ignore_index / label smoothing / mixed targets (cls_ce.hip).
+// The argument rules work on integers alone, so they are tested without a GPU (cls_ce_check): absent operands
+// have numel -1; dlogits_numel -1 is the forward.  Returns "" or "<fn>: <the rule>".
+std::string check_cls_ce_args(const std::string& fn, int64_t N, int64_t K, int64_t ldl, int64_t logits_numel,
+                              bool logits_f32, int64_t labels_numel, bool labels_i64, int64_t labels_b_numel,
+                              bool labels_b_i64, int64_t lam_numel, bool lam_f32, int64_t weight_numel,
+                              bool weight_f32, double eps, int64_t lse_numel, int64_t rows_numel, int64_t den_numel,
+                              int64_t dlogits_numel, int64_t go_numel) {
+  auto bad = [&](const std::string& why) { return fn + ": " + why; };
+  if (N < 1 || N > (1 << 30)) return bad("N must be >= 1 (and below 2^30)");
+  if (K < 1 || K > (1 << 30)) return bad("K must be >= 1 (and below 2^30)");
+  if (!logits_f32) return bad("logits must be fp32");
+  if (ldl < K || ldl > (1 << 30)) return bad("the row stride of the logits must be >= K");
+  if (logits_numel < (N - 1) * ldl + K) return bad("logits shorter than N rows of K");
+  if (!labels_i64 || (labels_b_numel >= 0 && !labels_b_i64)) return bad("labels must be int64");
+  if (labels_numel != N) return bad("labels must have N elements");
+  if ((labels_b_numel >= 0) != (lam_numel >= 0)) return bad("labels_b and lam come together");
+  if (labels_b_numel >= 0 && labels_b_numel != N) return bad("labels_b must have N elements");
+  if (lam_numel >= 0 && !lam_f32) return bad("lam must be fp32");
+  if (lam_numel >= 0 && lam_numel != 1 && lam_numel != N) return bad("lam must have 1 or N elements");
+  if (weight_numel >= 0 && !weight_f32) return bad("weight must be fp32");
+  if (weight_numel >= 0 && weight_numel != K) return bad("weight must have K elements");
+  if (!std::isfinite(eps)) return bad("label_smoothing must be finite");
+  if (eps < 0 || eps >= 1) return bad("label_smoothing must lie in [0, 1)");
+  if (lse_numel != N) return bad("lse must have N elements");
+  if (rows_numel != 3 * N) return bad("rows must have 3 N elements");
+  if (den_numel != 1) return bad("den must have 1 element");
+  if (dlogits_numel >= 0 && dlogits_numel != N * K) return bad("dlogits must have N K elements");
+  if (go_numel >= 0 && go_numel != 1) return bad("go must have 1 element");
+  return "";
+}
+static bool is_f32(const c10::optional<at::Tensor>& t) { return !given(t) || t->scalar_type() == at::kFloat; }
+static bool is_i64(const c10::optional<at::Tensor>& t) { return !given(t) || t->scalar_type() == at::kLong; }
+static void cls_ce_operands(const char* fn, std::initializer_list<const at::Tensor*> ts,
+                            std::initializer_list<const c10::optional<at::Tensor>*> os) {
+  auto ok = [&](const at::Tensor& t) {
+    if (!t.is_cuda() || !t.is_contiguous())
+      throw std::runtime_error(std::string(fn) + ": every operand must be a contiguous GPU tensor");
+  };
+  for (const at::Tensor* t : ts) ok(*t);
+  for (const c10::optional<at::Tensor>* o : os)
+    if (given(*o)) ok(**o);
+}
+void cls_ce_fwd(const at::Tensor& logits, int64_t ldl, const at::Tensor& labels,
+                const c10::optional<at::Tensor>& labels_b, const c10::optional<at::Tensor>& lam,
+                const c10::optional<at::Tensor>& weight, int64_t N, int64_t K, int64_t ignore_index, double eps,
+                at::Tensor lse, at::Tensor rows, at::Tensor loss, at::Tensor den) {
+  require_ok(check_cls_ce_args("cls_ce_fwd", N, K, ldl, logits.numel(), is_f32(logits), labels.numel(), is_i64(labels),
+                               onumel(labels_b), is_i64(labels_b), onumel(lam), is_f32(lam), onumel(weight),
+                               is_f32(weight), eps, lse.numel(), rows.numel(), den.numel(), -1, -1));
+  cls_ce_operands("cls_ce_fwd", {&labels, &lse, &rows, &loss, &den}, {&labels_b, &lam, &weight});
+  require_gpu(logits, "cls_ce_fwd logits");
+  f32_numel(lse, N, "cls_ce_fwd lse");
+  f32_numel(rows, 3 * N, "cls_ce_fwd rows");
+  f32_numel(loss, 1, "cls_ce_fwd loss");
+  f32_numel(den, 1, "cls_ce_fwd den");
+  check(dlmpi_cls_ce_fwd(ptr<float>(logits), (int)ldl, ptr<int64_t>(labels), optr<int64_t>(labels_b), optr<float>(lam),
+                         given(lam) && lam->numel() > 1 ? 1 : 0, optr<float>(weight), (int)N, (int)K, ignore_index,
+                         (float)eps, ptr<float>(lse), ptr<float>(rows), ptr<float>(loss), ptr<float>(den),
+                         cur_stream()),
+        "cls_ce_fwd");
+}
+void cls_ce_bwd(const at::Tensor& logits, int64_t ldl, const at::Tensor& labels,
+                const c10::optional<at::Tensor>& labels_b, const c10::optional<at::Tensor>& lam,
+                const c10::optional<at::Tensor>& weight, int64_t N, int64_t K, int64_t ignore_index, double eps,
+                const at::Tensor& lse, const at::Tensor& rows, const at::Tensor& den,
+                const c10::optional<at::Tensor>& go, at::Tensor dlogits) {
+  require_ok(check_cls_ce_args("cls_ce_bwd", N, K, ldl, logits.numel(), is_f32(logits), labels.numel(), is_i64(labels),
+                               onumel(labels_b), is_i64(labels_b), onumel(lam), is_f32(lam), onumel(weight),
+                               is_f32(weight), eps, lse.numel(), rows.numel(), den.numel(), dlogits.numel(),
+                               onumel(go)));
+  cls_ce_operands("cls_ce_bwd", {&labels, &lse, &rows, &den, &dlogits}, {&labels_b, &lam, &weight, &go});
+  require_gpu(logits, "cls_ce_bwd logits");
+  f32_numel(lse, N, "cls_ce_bwd lse");
+  f32_numel(rows, 3 * N, "cls_ce_bwd rows");
+  f32_numel(den, 1, "cls_ce_bwd den");
+  f32_numel(dlogits, N * K, "cls_ce_bwd dlogits");
+  if (given(go)) f32_numel(*go, 1, "cls_ce_bwd go");
+  check(dlmpi_cls_ce_bwd(ptr<float>(logits), (int)ldl, ptr<int64_t>(labels), optr<int64_t>(labels_b), optr<float>(lam),
+                         given(lam) && lam->numel() > 1 ? 1 : 0, optr<float>(weight), (int)N, (int)K, ignore_index,
+                         (float)eps, ptr<float>(lse), ptr<float>(rows), ptr<float>(den), optr<float>(go),
+                         ptr<float>(dlogits), cur_stream()),
+        "cls_ce_bwd");
+}
+
 // The preambles of the four pixel-loss binders (fn: the binder's name, kept in the error texts).  tab: the fused
 // loss's Dice table [N][K][2], null for the cross-entropy alone; loss: null when the backward's preamble calls.
 static void pix_fwd_check(const std::string& fn, const at::Tensor& logits, int64_t sn, int64_t sk, int64_t sp, int N,
@@ -697,6 +782,57 @@ void image_batch(const at::Tensor& data, const at::Tensor& labels, const at::Ten
         "image_batch");
 }
 
+// The mixed batch of the device-resident pipeline and the in-place mix of any fp32 NCHW batch (data.hip); kind
+// 0 none / 1 mixup / 2 CutMix with the box rows [y0, y1) x columns [x0, x1) inside the image.
+static void batch_labels_ok(const char* fn, const char* name, const at::Tensor& t, int B) {
+  if (t.scalar_type() != at::kLong || !t.is_contiguous() || t.numel() != B || !t.is_cuda())
+    throw std::runtime_error(std::string(fn) + ": " + name + " must be contiguous int64 [B] on the GPU");
+}
+static void mix_args_ok(const char* fn, int kind, double lam, int H, int W, int y0, int y1, int x0, int x1,
+                        const at::Tensor& labels_a, const at::Tensor& labels_b, const at::Tensor& lam_out, int B) {
+  if (kind < 0 || kind > 2) throw std::runtime_error(std::string(fn) + ": kind must be 0, 1 or 2");
+  if (!(lam >= 0 && lam <= 1)) throw std::runtime_error(std::string(fn) + ": lam must lie in [0, 1]");
+  if (y0 < 0 || y1 < y0 || y1 > H || x0 < 0 || x1 < x0 || x1 > W)
+    throw std::runtime_error(std::string(fn) + ": the box must lie inside the image");
+  batch_labels_ok(fn, "labels", labels_a, B);
+  batch_labels_ok(fn, "labels_b", labels_b, B);
+  f32_numel(lam_out, 1, (std::string(fn) + " lam").c_str());
+}
+void image_batch_mix(const at::Tensor& data, const at::Tensor& labels, const at::Tensor& idx, int H, int W, int C,
+                     int pad, bool augment, int64_t seed, int64_t epoch, std::vector<double> mean,
+                     std::vector<double> sd, int kind, double lam, int y0, int y1, int x0, int x1, at::Tensor out,
+                     at::Tensor out_labels, at::Tensor labels_b, at::Tensor lam_out) {
+  require_gpu(data, "data");
+  if (mean.size() != (size_t)C || sd.size() != (size_t)C || C < 1 || C > 3)
+    throw std::runtime_error("image_batch_mix: mean/std per channel, 1..3 channels");
+  if (data.scalar_type() != at::kByte || idx.scalar_type() != at::kLong || out.scalar_type() != at::kFloat ||
+      labels.scalar_type() != at::kLong)
+    throw std::runtime_error("image_batch_mix: uint8 data, int64 labels and indices, fp32 output");
+  float m3[3] = {0.f, 0.f, 0.f}, s3[3] = {1.f, 1.f, 1.f};
+  for (int c = 0; c < C; ++c) { m3[c] = (float)mean[c]; s3[c] = (float)sd[c]; }
+  const int B = (int)idx.numel();
+  if (B < 1 || H < 1 || W < 1) throw std::runtime_error("image_batch_mix: empty batch");
+  if (!idx.is_contiguous() || !idx.is_cuda() || !out.is_contiguous() || !out.is_cuda() ||
+      out.numel() != (int64_t)B * C * H * W)
+    throw std::runtime_error("image_batch_mix: contiguous GPU indices and a contiguous fp32 [B, C, H, W] GPU output");
+  mix_args_ok("image_batch_mix", kind, lam, H, W, y0, y1, x0, x1, out_labels, labels_b, lam_out, B);
+  check(dlmpi_image_batch_mix(ptr<uint8_t>(data), ptr<int64_t>(labels), ptr<int64_t>(idx), B, H, W, C, pad,
+                              augment ? 1 : 0, (uint32_t)seed, (uint32_t)epoch, m3, s3, kind, (float)lam, y0, y1, x0,
+                              x1, ptr<float>(out), ptr<int64_t>(out_labels), ptr<int64_t>(labels_b),
+                              ptr<float>(lam_out), cur_stream()),
+        "image_batch_mix");
+}
+void mix_batch_(at::Tensor x, const at::Tensor& labels, int kind, double lam, int y0, int y1, int x0, int x1,
+                at::Tensor labels_b, at::Tensor lam_out) {
+  if (x.dim() != 4 || x.scalar_type() != at::kFloat || !x.is_contiguous() || !x.is_cuda() || x.numel() < 1)
+    throw std::runtime_error("mix_batch_: x must be a contiguous fp32 [B, C, H, W] GPU tensor");
+  const int B = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
+  mix_args_ok("mix_batch_", kind, lam, H, W, y0, y1, x0, x1, labels, labels_b, lam_out, B);
+  check(dlmpi_mix_batch(ptr<float>(x), ptr<int64_t>(labels), B, C, H, W, kind, (float)lam, y0, y1, x0, x1,
+                        ptr<int64_t>(labels_b), ptr<float>(lam_out), cur_stream()),
+        "mix_batch_");
+}
+
 void register_ops(pybind11::module& m) {
   namespace py = pybind11;
   register_conv_fwd(m);
@@ -751,6 +887,16 @@ void register_ops(pybind11::module& m) {
   m.def("cast_weights", &cast_weights);
   m.def("softmax_ce_fwd", &softmax_ce_fwd);
   m.def("softmax_ce_bwd", &softmax_ce_bwd);
+  m.def("cls_ce_fwd", &cls_ce_fwd);
+  m.def("cls_ce_bwd", &cls_ce_bwd);
+  m.def("cls_ce_check", &check_cls_ce_args, py::arg("fn") = "cls_ce_fwd", py::arg("N"), py::arg("K"), py::arg("ldl"),
+        py::arg("logits_numel"), py::arg("logits_f32") = true, py::arg("labels_numel"), py::arg("labels_i64") = true,
+        py::arg("labels_b_numel") = -1, py::arg("labels_b_i64") = true, py::arg("lam_numel") = -1,
+        py::arg("lam_f32") = true, py::arg("weight_numel") = -1, py::arg("weight_f32") = true, py::arg("eps") = 0.0,
+        py::arg("lse_numel"), py::arg("rows_numel"), py::arg("den_numel") = 1, py::arg("dlogits_numel") = -1,
+        py::arg("go_numel") = -1);
+  m.def("image_batch_mix", &image_batch_mix);
+  m.def("mix_batch_", &mix_batch_);
   m.def("bce_fwd", &bce_fwd);
   m.def("bce_bwd", &bce_bwd);
   m.def("argmax_correct", &argmax_correct);

@@ -409,6 +409,18 @@ hipError_t dlmpi_bce_fwd(const float* logits, int ldl, const float* target, int6
 hipError_t dlmpi_bce_bwd(const float* logits, int ldl, const float* target, int64_t M, const float* go, float scale,
                          float* dlogits, hipStream_t s);
 hipError_t dlmpi_sum_f32(const float* x, int64_t n, float* out, float scale, hipStream_t s);
+// classification cross-entropy with weight / ignore_index / label smoothing and two-label mixed targets
+// (cls_ce.hip): logits fp32 [N] rows of K at stride ldl, labels int64 [N], labels_b int64 [N] or null (b = a),
+// lam fp32 at n * lam_stride (lam_stride 0 or 1) or null (lam = 1), weight fp32 [K] or null, 0 <= eps < 1.
+// The forward writes lse [N], rows [N][3] = {numerator, denominator, S_n} per row, loss and den[0] = D;
+// the backward writes dlogits fp32 [N][K] = (go / D) (S_n softmax - w q), zeros where nothing is kept.
+hipError_t dlmpi_cls_ce_fwd(const float* logits, int ldl, const int64_t* labels, const int64_t* labels_b,
+                            const float* lam, int lam_stride, const float* weight, int N, int K, int64_t ignore_index,
+                            float eps, float* lse, float* rows, float* loss, float* den, hipStream_t s);
+hipError_t dlmpi_cls_ce_bwd(const float* logits, int ldl, const int64_t* labels, const int64_t* labels_b,
+                            const float* lam, int lam_stride, const float* weight, int N, int K, int64_t ignore_index,
+                            float eps, const float* lse, const float* rows, const float* den, const float* go,
+                            float* dlogits, hipStream_t s);
 // pixel-wise softmax cross-entropy over N x HW pixels and K = 2..256 classes (pixel_ce.hip; what it
 // shares with seg_dice.hip is in pixel_softmax.h): logits fp32 at n*sn + k*sk + p*sp (elements), labels int64 [N*HW] (ignore_index or outside [0, K): ignored), weight
 // fp32 [K] or null; lse [N*HW], partial [dlmpi_pixel_ce_blocks(N*HW)][2], loss = sum w nll / sum w, den = sum w
@@ -491,6 +503,16 @@ hipError_t dlmpi_lamb_update(float* p, const float* m, const float* v, const int
 hipError_t dlmpi_image_batch(const uint8_t* data, const int64_t* labels, const int64_t* idx, int B, int H, int W,
                              int C, int pad, int augment, uint32_t seed, uint32_t epoch, const float* mean3,
                              const float* std3, float* out, int64_t* out_labels, hipStream_t s);
+
+// the same batch mixed with mixup (kind 1) or CutMix (kind 2, box rows [y0, y1) x columns [x0, x1)); kind 0: not
+// mixed.  Sample b pairs with B - 1 - b; also writes labels_b[b] = labels[idx[B - 1 - b]] and lam_out[0] = lam.
+hipError_t dlmpi_image_batch_mix(const uint8_t* data, const int64_t* labels, const int64_t* idx, int B, int H, int W,
+                                 int C, int pad, int augment, uint32_t seed, uint32_t epoch, const float* mean3,
+                                 const float* std3, int kind, float lam, int y0, int y1, int x0, int x1, float* out,
+                                 int64_t* out_labels, int64_t* labels_b, float* lam_out, hipStream_t s);
+// in-place mix of a contiguous fp32 [B][C][H][W] batch; labels_b[b] = labels[B - 1 - b], lam_out[0] = lam
+hipError_t dlmpi_mix_batch(float* x, const int64_t* labels, int B, int C, int H, int W, int kind, float lam, int y0,
+                           int y1, int x0, int x1, int64_t* labels_b, float* lam_out, hipStream_t s);
 
 // fault injection: keep stream s busy for `ms` milliseconds (bounded; tests of the watchdog)
 hipError_t dlmpi_delay(double ms, hipStream_t s);

@@ -2,3 +2,4 @@ from .datasets import (CIFAR10, CarvanaDataset, CifarTransform, SegmentationData
                        SyntheticImages, SyntheticMasks, device_batch)
 from .sampler import DistributedSampler  # noqa: F401
 from .device import DeviceBatches, DeviceCachedDataset, DeviceImageDataset, image_batch_reference  # noqa: F401
+from .mix import MixConfig, MixParams, draw_mix, mix_batch_, mix_reference  # noqa: F401

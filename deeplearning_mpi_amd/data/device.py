@@ -12,6 +12,8 @@ device-side gather:
   + ToTensor + Normalize (the reference CIFAR transform), written as fp32 NCHW.  The augmentation
   parameters are a hash of (seed, epoch, dataset index), so they do not depend on the batch size,
   rank count or worker count, and :func:`image_batch_reference` reproduces them exactly on the CPU.
+  With ``mix=MixConfig(...)`` the same kernel also mixes the batch with itself (mixup / CutMix,
+  ``data/mix.py``): "augment as today, then mix", and it writes ``labels_b`` and the device ``lam``.
 * :class:`DeviceCachedDataset` -- any deterministic map-style dataset (the reference UNet's
   image/mask dataset has no random augmentation) materialised once on the device; batches are
   ``index_select`` gathers.
@@ -25,6 +27,7 @@ import numpy as np
 import torch
 
 from .datasets import CIFAR10, CIFAR_MEAN, CIFAR_STD
+from .mix import KINDS, MixConfig, draw_mix, mix_reference
 
 _M32 = 0xFFFFFFFF
 
@@ -70,7 +73,8 @@ class DeviceImageDataset:
     """uint8 images [N, H, W, C] + int64 labels resident on ``device``; ``batch`` assembles
     normalised (optionally crop/flip-augmented) fp32 NCHW batches with one kernel."""
 
-    def __init__(self, images_hwc_u8, labels, device, augment=False, pad=4, mean=CIFAR_MEAN, std=CIFAR_STD, seed=0):
+    def __init__(self, images_hwc_u8, labels, device, augment=False, pad=4, mean=CIFAR_MEAN, std=CIFAR_STD, seed=0,
+                 mix: MixConfig = None):
         self.device = torch.device(device)
         self.data = torch.as_tensor(np.ascontiguousarray(images_hwc_u8)).to(self.device)
         self.labels = torch.as_tensor(np.asarray(labels, dtype=np.int64)).to(self.device)
@@ -78,6 +82,7 @@ class DeviceImageDataset:
         self.N, self.H, self.W, self.C = self.data.shape
         self.augment, self.pad, self.seed = augment, pad, seed
         self.mean, self.std = list(mean)[:self.C], list(std)[:self.C]
+        self.mix = mix
         self._native = None
         if self.device.type == "cuda":
             from .._ext import native
@@ -85,16 +90,20 @@ class DeviceImageDataset:
             self._native = native()
 
     @classmethod
-    def cifar10(cls, root, train, device, augment=None, seed=0):
+    def cifar10(cls, root, train, device, augment=None, seed=0, mix=None):
         data, targets = CIFAR10._load(root, train)
-        return cls(data, targets, device, augment=train if augment is None else augment, seed=seed)
+        return cls(data, targets, device, augment=train if augment is None else augment, seed=seed, mix=mix)
 
     def __len__(self):
         return self.N
 
-    def batch(self, idx: torch.Tensor, epoch: int = 0, out=None):
-        """idx: int64 dataset indices on the device -> (x [B, C, H, W] fp32, y [B] int64)."""
+    def batch(self, idx: torch.Tensor, epoch: int = 0, out=None, batch_no: int = 0, rank: int = 0):
+        """idx: int64 dataset indices on the device -> (x [B, C, H, W] fp32, y [B] int64); with ``mix`` set ->
+        (x, labels_a, labels_b [B] int64, lam [1] fp32), mixed as ``draw_mix(mix, seed, epoch, rank, batch_no)``
+        says."""
         B = idx.numel()
+        if self.mix is not None:
+            return self._mixed_batch(idx, epoch, out, batch_no, rank)
         if out is None:
             x = torch.empty(B, self.C, self.H, self.W, dtype=torch.float32, device=self.device)
             y = torch.empty(B, dtype=torch.int64, device=self.device)
@@ -109,6 +118,29 @@ class DeviceImageDataset:
             x.copy_(xr)
             y.copy_(yr)
         return x, y
+
+    def _mixed_batch(self, idx, epoch, out, batch_no, rank):
+        B = idx.numel()
+        if out is None:
+            x = torch.empty(B, self.C, self.H, self.W, dtype=torch.float32, device=self.device)
+            ya = torch.empty(B, dtype=torch.int64, device=self.device)
+            yb, lam = torch.empty_like(ya), torch.empty(1, dtype=torch.float32, device=self.device)
+        else:
+            x, ya, yb, lam = out
+        p = draw_mix(self.mix, self.seed, epoch, rank, batch_no, self.H, self.W)
+        if self._native is not None:
+            self._native.image_batch_mix(self.data, self.labels, idx, self.H, self.W, self.C, self.pad, self.augment,
+                                         self.seed, epoch, self.mean, self.std, KINDS.index(p.kind), float(p.lam),
+                                         *p.box, x, ya, yb, lam)
+        else:
+            xr, yr = image_batch_reference(self.data, self.labels, idx, self.pad, self.augment, self.seed, epoch,
+                                           self.mean, self.std)
+            xm, _, ybr, lr = mix_reference(xr, yr, p)
+            x.copy_(xm)
+            ya.copy_(yr)
+            yb.copy_(ybr)
+            lam.copy_(lr)
+        return x, ya, yb, lam
 
 
 class DeviceCachedDataset:
@@ -153,6 +185,7 @@ class DeviceBatches:
 
     def __init__(self, dataset, batch_size, sampler=None, drop_last=False, out=None):
         self.ds, self.bs, self.sampler, self.drop_last, self.out = dataset, batch_size, sampler, drop_last, out
+        self.mixed = getattr(dataset, "mix", None) is not None   # batches are (x, labels_a, labels_b, lam)
 
     def __len__(self):
         n = len(self.sampler) if self.sampler is not None else len(self.ds)
@@ -163,9 +196,14 @@ class DeviceBatches:
         epoch = getattr(self.sampler, "epoch", 0)
         idx = torch.tensor(order, dtype=torch.int64).to(self.ds.device, non_blocking=True)
         n = idx.numel()
-        for s in range(0, n, self.bs):
+        rank = getattr(self.sampler, "rank", 0)
+        for no, s in enumerate(range(0, n, self.bs)):
             e = min(n, s + self.bs)
             if e - s < self.bs and self.drop_last:
                 break
             full = e - s == self.bs
-            yield self.ds.batch(idx[s:e], epoch, out=self.out if (full and self.out is not None) else None)
+            out = self.out if (full and self.out is not None) else None
+            if self.mixed:   # the mix is drawn per (seed, epoch, rank, batch number)
+                yield self.ds.batch(idx[s:e], epoch, out=out, batch_no=no, rank=rank)
+            else:
+                yield self.ds.batch(idx[s:e], epoch, out=out)

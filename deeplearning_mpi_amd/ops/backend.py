@@ -462,6 +462,26 @@ class NativeBackend:
         self.C.softmax_ce_bwd(logits, logits.stride(0), labels, lse, N, K, K, go, 1.0 / N, d)
         return d
 
+    def cls_ce_fwd(self, logits, labels, weight=None, ignore_index=-100, label_smoothing=0.0, labels_b=None,
+                   lam=None):
+        """Classification cross-entropy with weight / ignore_index / label smoothing and mixed targets
+        (ops/losses.py cross_entropy): logits fp32 [N, K] with unit column stride -> (loss, lse [N], rows [N, 3] =
+        per-row {numerator, denominator, S_n}, den [1])."""
+        N, K = logits.shape
+        lse = torch.empty(N, dtype=torch.float32, device=logits.device)
+        rows, loss, den = lse.new_empty(N, 3), lse.new_empty(()), lse.new_empty(1)
+        self.C.cls_ce_fwd(logits, logits.stride(0) if N > 1 else K, labels, labels_b, lam, weight, N, K,
+                          int(ignore_index), float(label_smoothing), lse, rows, loss, den)
+        return loss, lse, rows, den
+
+    def cls_ce_bwd(self, logits, labels, lse, rows, den, go, weight=None, ignore_index=-100, label_smoothing=0.0,
+                   labels_b=None, lam=None):
+        N, K = logits.shape
+        d = torch.empty(N, K, dtype=torch.float32, device=logits.device)
+        self.C.cls_ce_bwd(logits, logits.stride(0) if N > 1 else K, labels, labels_b, lam, weight, N, K,
+                          int(ignore_index), float(label_smoothing), lse, rows, den, go, d)
+        return d
+
     def _pixel_fwd_out(self, logits):   # what every pixel-loss forward fills: lse [N*H*W], loss (scalar), den [1]
         lse = torch.empty(logits.numel() // logits.shape[1], dtype=torch.float32, device=logits.device)
         return lse, lse.new_empty(()), lse.new_empty(1)
@@ -905,6 +925,37 @@ class RefBackend:
         p = torch.exp(logits.to(self.dt) - lse[:, None])
         p[torch.arange(len(labels)), labels] -= 1.0
         return p * (go if go is not None else 1.0) / logits.shape[0]
+
+    def _cls_terms(self, logits, labels, weight, ignore_index, eps, labels_b, lam):
+        """The closed form of the classification loss: (x, w [K], q [N, K], D)."""
+        x = logits.to(self.dt)
+        N, K = x.shape
+        a = labels
+        b = labels_b if labels_b is not None else labels
+        l = lam.to(self.dt).reshape(-1).expand(N) if lam is not None else torch.ones(N, dtype=self.dt, device=x.device)
+        w = weight.to(self.dt) if weight is not None else torch.ones(K, dtype=self.dt, device=x.device)
+        la = l * self._pix_keep(a, K, ignore_index)
+        lb = (1 - l) * self._pix_keep(b, K, ignore_index)
+        t = (la[:, None] * F.one_hot(a.clamp(0, K - 1), K) + lb[:, None] * F.one_hot(b.clamp(0, K - 1), K)).to(self.dt)
+        q = (1 - eps) * t + (eps / K) * (la + lb)[:, None]
+        return x, w, q, (t * w).sum()
+
+    def cls_ce_fwd(self, logits, labels, weight=None, ignore_index=-100, label_smoothing=0.0, labels_b=None,
+                   lam=None):
+        x, w, q, D = self._cls_terms(logits, labels, weight, ignore_index, label_smoothing, labels_b, lam)
+        lse = torch.logsumexp(x, 1)
+        wq = w * q
+        rows = torch.stack([(wq * (lse[:, None] - x)).sum(1), torch.zeros_like(lse), wq.sum(1)], 1)
+        return rows[:, 0].sum() / D, lse, rows, D.reshape(1)
+
+    def cls_ce_bwd(self, logits, labels, lse, rows, den, go, weight=None, ignore_index=-100, label_smoothing=0.0,
+                   labels_b=None, lam=None):
+        x, w, q, D = self._cls_terms(logits, labels, weight, ignore_index, label_smoothing, labels_b, lam)
+        wq = w * q
+        d = wq.sum(1, keepdim=True) * torch.exp(x - lse[:, None]) - wq
+        d = torch.where(q.sum(1, keepdim=True) != 0, d, torch.zeros_like(d))   # rows without a kept label: exact zeros
+        g = (go if go is not None else 1.0) / D
+        return d * g if float(D) != 0 else torch.zeros_like(d)
 
     @staticmethod
     def _pix_keep(labels, K, ignore_index):

@@ -117,16 +117,73 @@ def _check_pixel_args(logits, labels, weight=None):
         raise ValueError(f"weight has {weight.numel()} entries for {logits.shape[1]} classes")
 
 
-def cross_entropy(logits, labels, weight=None, ignore_index=-100):
+class _ClsCE(torch.autograd.Function):
+    """Classification cross-entropy with weight / ignore_index / label smoothing and two-label mixed targets
+    (csrc/kernels/cls_ce.hip).  ``labels_b`` and ``lam`` are read in place by both passes, so a replayed graph
+    follows what they hold at replay time; the buffers are ``empty`` and no ATen kernel is launched."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, ignore_index, label_smoothing, labels_b, lam):
+        be = _be(logits.device, logits.dtype)
+        x = logits.contiguous().to(be.dt)
+        w = weight.to(be.dt).contiguous() if weight is not None else None
+        lam = lam.to(be.dt) if lam is not None else None
+        loss, lse, rows, den = be.cls_ce_fwd(x, labels, w, ignore_index, label_smoothing, labels_b, lam)
+        ctx.save_for_backward(x, labels, lse, rows, den, w, labels_b, lam)
+        ctx.ignore_index, ctx.label_smoothing, ctx.in_dtype = ignore_index, label_smoothing, logits.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, go):
+        x, labels, lse, rows, den, w, labels_b, lam = ctx.saved_tensors
+        be = _be(x.device, x.dtype)
+        g = be.cls_ce_bwd(x, labels, lse, rows, den, go.reshape(1).to(be.dt).contiguous(), w, ctx.ignore_index,
+                          ctx.label_smoothing, labels_b, lam)
+        return (g.to(ctx.in_dtype),) + (None,) * 6
+
+
+def _check_cls_args(logits, labels, weight, label_smoothing, labels_b, lam):
+    if logits.dim() != 2:
+        raise ValueError(f"cross_entropy takes [N, K] or [N, K, H, W] logits, got {tuple(logits.shape)}")
+    N, K = logits.shape
+    if (labels_b is None) != (lam is None):
+        raise ValueError("labels_b and lam come together: a mixed target needs both")
+    for name, y in (("labels", labels), ("labels_b", labels_b)):
+        if y is not None and (y.dtype != torch.int64 or y.shape != (N,)):
+            raise ValueError(f"[N, K] logits need int64 {name} [N], got {y.dtype} {tuple(y.shape)}")
+    if lam is not None and (not torch.is_tensor(lam) or not lam.is_floating_point() or lam.numel() not in (1, N)
+                            or lam.device != logits.device):
+        raise ValueError("lam must be a float tensor of 1 or N elements on the device of the logits")
+    if weight is not None and weight.numel() != K:
+        raise ValueError(f"weight has {weight.numel()} entries for {K} classes")
+    if not (math.isfinite(label_smoothing) and 0 <= label_smoothing < 1):
+        raise ValueError(f"label_smoothing must lie in [0, 1), got {label_smoothing}")
+
+
+def cross_entropy(logits, labels, weight=None, ignore_index=-100, label_smoothing=0.0, labels_b=None, lam=None):
     """Mean softmax cross-entropy.  [N, K] logits with [N] labels: the classification loss;
-    [N, K, H, W] logits with [N, H, W] labels: the pixel-wise loss with torch's ``weight`` /
-    ``ignore_index`` semantics (labels outside [0, K) are ignored as well)."""
+    [N, K, H, W] logits with [N, H, W] labels: the pixel-wise loss.  Both take torch's ``weight`` /
+    ``ignore_index`` semantics (labels outside [0, K) are ignored as well).
+
+    The classification loss also takes ``label_smoothing`` (torch's) and a two-label mixed target for mixup /
+    CutMix: ``labels_b`` int64 [N] with ``lam``, a float32 tensor of 1 or N elements on the device.  With
+    keep(y) = y is neither ``ignore_index`` nor outside [0, K):
+    t[c] = lam [a = c] keep(a) + (1 - lam) [b = c] keep(b), m = lam keep(a) + (1 - lam) keep(b),
+    q[c] = (1 - eps) t[c] + (eps / K) m, and loss = - sum_n sum_c w_c q_n[c] log softmax_n[c] / sum_n sum_c w_c t_n[c]
+    (NaN when nothing is kept, as torch).  ``lam`` stays on the device -- a replayed graph reads its current
+    value -- and is trusted to lie in [0, 1]: checking it would need a host synchronisation.
+    A call with every default runs the plain classification kernels (mean over N)."""
     if logits.dim() == 4:
+        if label_smoothing != 0 or labels_b is not None or lam is not None:
+            raise NotImplementedError("label_smoothing / labels_b / lam are implemented for classification ([N, K]) "
+                                      "logits, not for pixel-wise ([N, K, H, W]) logits")
         _check_pixel_args(logits, labels, weight)
         return _PixelCE.apply(logits, labels, weight, int(ignore_index))
-    if weight is not None or ignore_index != -100:
-        raise NotImplementedError("weight / ignore_index are implemented for pixel-wise ([N, K, H, W]) logits")
-    return _CE.apply(logits, labels)
+    if weight is None and ignore_index == -100 and label_smoothing == 0 and labels_b is None and lam is None:
+        return _CE.apply(logits, labels)
+    label_smoothing = float(label_smoothing)
+    _check_cls_args(logits, labels, weight, label_smoothing, labels_b, lam)
+    return _ClsCE.apply(logits, labels, weight, int(ignore_index), label_smoothing, labels_b, lam)
 
 
 def bce_with_logits(logits, target):
@@ -265,13 +322,13 @@ class DiceLoss(nn.Module):
 
 
 class CrossEntropyLoss(nn.Module):
-    def __init__(self, weight=None, ignore_index=-100):
+    def __init__(self, weight=None, ignore_index=-100, label_smoothing=0.0):
         super().__init__()
         self.register_buffer("weight", weight)
-        self.ignore_index = ignore_index
+        self.ignore_index, self.label_smoothing = ignore_index, label_smoothing
 
-    def forward(self, logits, labels):
-        return cross_entropy(logits, labels, self.weight, self.ignore_index)
+    def forward(self, logits, labels, labels_b=None, lam=None):
+        return cross_entropy(logits, labels, self.weight, self.ignore_index, self.label_smoothing, labels_b, lam)
 
 
 class BCEWithLogitsLoss(nn.Module):
