@@ -17,6 +17,9 @@ trains UNet(out_classes=K) on the integer class-index masks with the pixel-wise 
 sigmoid form for --num_classes 1, softmax form for K > 1 (ops.bce_dice_loss / ce_dice_loss / dice_loss;
 --dice_weight, --dice_smooth, --dice_background 0 to leave class 0 out of the mean).  On the GPU the Dice
 sums and gradient ride in the cross-entropy kernels' passes: one forward, one finish, one backward.
+--aug_hflip / --aug_vflip / --aug_scale / --aug_rotate / --aug_translate / --aug_prob (defaults: none) augment
+the training split on the device: the pairs stay resident and one kernel per batch gathers and resamples image
+and mask (data/seg_aug.py, DeviceSegDataset); evaluation is unchanged.
 """
 from __future__ import annotations
 
@@ -33,7 +36,8 @@ from torch.utils.data import DataLoader
 from tqdm import tqdm
 
 from .. import parallel
-from ..data import CarvanaDataset, DeviceBatches, DeviceCachedDataset, DistributedSampler, SyntheticMasks
+from ..data import (CarvanaDataset, DeviceBatches, DeviceCachedDataset, DeviceSegDataset, DistributedSampler,
+                    SegAugConfig, SyntheticMasks)
 from ..models import UNet
 from ..ops import (BCEDiceLoss, BCEWithLogitsLoss, CEDiceLoss, CrossEntropyLoss, DiceLoss, backward, dice_multiclass,
                    dice_per_sample)
@@ -90,6 +94,15 @@ def build_argparser() -> argparse.ArgumentParser:
                         "eagerly); auto = on for launch-bound GPU training")
     p.add_argument("--benchmark_steps", type=int, default=0,
                    help="time this many steps on a synthetic device batch, print images/sec and exit")
+    p.add_argument("--aug_hflip", type=float, default=0.0, help="probability of a horizontal flip of a training sample")
+    p.add_argument("--aug_vflip", type=float, default=0.0, help="probability of a vertical flip")
+    p.add_argument("--aug_scale", type=float, nargs=2, default=[1.0, 1.0], metavar=("LO", "HI"),
+                   help="isotropic zoom, log-uniform in [LO, HI]")
+    p.add_argument("--aug_rotate", type=float, default=0.0, help="rotation uniform in +-DEG degrees")
+    p.add_argument("--aug_translate", type=float, default=0.0,
+                   help="translation uniform in +-F of the image width / height")
+    p.add_argument("--aug_prob", type=float, default=1.0,
+                   help="probability that a sample gets its scale / rotation / translation (flips are drawn apart)")
     add_layerwise_args(p, "adam", "lamb")
     p.add_argument("--weight_decay", type=float, default=None,
                    help="weight decay (default: 0 for adam, 0.01 for lamb)")
@@ -141,6 +154,13 @@ def evaluate_model(model, device, test_loader, num_classes=1, ignore_index=-100)
     return torch.cat(scores).mean().item()
 
 
+def seg_aug_config(args) -> SegAugConfig:
+    """The --aug_* flags (absent on namespaces that callers build themselves: the defaults, no augmentation)."""
+    return SegAugConfig(hflip=getattr(args, "aug_hflip", 0.0), vflip=getattr(args, "aug_vflip", 0.0),
+                        scale=tuple(getattr(args, "aug_scale", (1.0, 1.0))), rotate=getattr(args, "aug_rotate", 0.0),
+                        translate=getattr(args, "aug_translate", 0.0), prob=getattr(args, "aug_prob", 1.0))
+
+
 def build_data_loaders(args, device):
     if args.synthetic:
         ds = SyntheticMasks(args.synthetic_size, (args.in_channels, args.image_size, args.image_size),
@@ -157,6 +177,18 @@ def build_data_loaders(args, device):
     # same split on every rank (seeded generator rather than the global RNG)
     train_ds, test_ds = torch.utils.data.random_split(ds, [train_size, test_size],
                                                       generator=torch.Generator().manual_seed(args.random_seed))
+    aug = seg_aug_config(args)
+    if aug.enabled:
+        # geometric augmentation of the training split: the pairs stay in device memory and one kernel per batch
+        # gathers and resamples them (evaluation is untouched); outside the source the multi-class mask carries
+        # --ignore_index, which the losses and the Dice counts leave out
+        if args.data_on_device == "0":
+            raise ValueError("the --aug_* flags augment on the device: they cannot go with --data_on_device 0")
+        train_c = DeviceSegDataset(train_ds, device, aug, seed=args.random_seed,
+                                   mask_fill=args.ignore_index if args.num_classes > 1 else 0.0)
+        test_c = DeviceCachedDataset(test_ds, device)
+        sampler = DistributedSampler(train_c)
+        return DeviceBatches(train_c, args.batch_size, sampler), DeviceBatches(test_c, args.batch_size), sampler
     if _use_device_data(args, device, ds):
         # the reference dataset is deterministic (no augmentation): decode / resize once, keep the
         # tensors in HBM, and serve every batch as an index gather on the device
@@ -293,6 +325,11 @@ def run(args) -> dict:
     if args.graph and device.type == "cuda":
         captured = CapturedStep(lambda: train_step(x_static, y_static), warmup=2, inputs=(x_static, y_static),
                                 comm=comm)
+        seg = getattr(train_loader, "ds", None)
+        if isinstance(seg, DeviceSegDataset) and (seg.C, seg.Ho, seg.Wo) == tuple(x_static.shape[1:]):
+            # the batch kernel writes full batches straight into the captured step's inputs (set_inputs then
+            # has nothing to copy); it runs outside the captured graph
+            train_loader.out = (x_static, y_static)
     if args.benchmark_steps:
         return benchmark(args, train_step, captured, x_static, y_static, comm, device)
     history = {"loss": [], "dice": []}
@@ -359,6 +396,12 @@ def parse_args(argv=None):
     if args.num_classes < 1:
         p.error(f"--num_classes must be >= 1, got {args.num_classes}")
     check_layerwise_args(p, args, "adam")
+    try:
+        aug = seg_aug_config(args)
+    except ValueError as e:
+        p.error(f"--aug_*: {e}")
+    if aug.enabled and args.data_on_device == "0":
+        p.error("the --aug_* flags augment on the device: they cannot go with --data_on_device 0")
     return args
 
 

@@ -833,6 +833,47 @@ void mix_batch_(at::Tensor x, const at::Tensor& labels, int kind, double lam, in
         "mix_batch_");
 }
 
+// Segmentation augmentation (seg_aug.hip): images fp32 [N, C, H, W] and masks [N, H, W] (float32 | int64) gathered
+// by idx [B] and resampled through rows idx[b] of table (int32 [N, 6], Q16) into out [B, C, Ho, Wo] and out_mask
+// [B, Ho, Wo].  idx values are trusted.
+static void seg_arg_ok(const char* name, const at::Tensor& t, at::ScalarType type, const char* tname,
+                       std::vector<int64_t> shape) {
+  std::string want;
+  for (size_t i = 0; i < shape.size(); ++i) want += (i ? ", " : "") + std::to_string(shape[i]);
+  if (!t.is_cuda() || t.scalar_type() != type || !t.is_contiguous() || t.sizes().vec() != shape)
+    throw std::runtime_error(std::string("seg_aug_batch: ") + name + " must be a contiguous " + tname + " [" + want +
+                             "] GPU tensor");
+}
+void seg_aug_batch(const at::Tensor& images, const at::Tensor& masks, const at::Tensor& idx, const at::Tensor& table,
+                   double image_fill, double mask_fill, at::Tensor out, at::Tensor out_mask) {
+  if (!images.is_cuda() || images.scalar_type() != at::kFloat || !images.is_contiguous() || images.dim() != 4 ||
+      images.numel() < 1)
+    throw std::runtime_error("seg_aug_batch: images must be a contiguous fp32 [N, C, H, W] GPU tensor");
+  const int64_t N = images.size(0), C = images.size(1), H = images.size(2), W = images.size(3);
+  const bool i64 = masks.scalar_type() == at::kLong;
+  if (!i64 && masks.scalar_type() != at::kFloat)
+    throw std::runtime_error("seg_aug_batch: masks must be float32 or int64");
+  const at::ScalarType mt = i64 ? at::kLong : at::kFloat;
+  const char* mname = i64 ? "int64" : "fp32";
+  seg_arg_ok("masks", masks, mt, mname, {N, H, W});
+  if (!idx.is_cuda() || idx.scalar_type() != at::kLong || !idx.is_contiguous() || idx.dim() != 1 || idx.numel() < 1)
+    throw std::runtime_error("seg_aug_batch: idx must be a contiguous int64 [B] GPU tensor, B >= 1");
+  seg_arg_ok("table", table, at::kInt, "int32", {N, 6});
+  if (out.dim() != 4 || out.numel() < 1)
+    throw std::runtime_error("seg_aug_batch: out must be a contiguous fp32 [B, C, Ho, Wo] GPU tensor");
+  const int64_t B = idx.numel(), Ho = out.size(2), Wo = out.size(3);
+  seg_arg_ok("out", out, at::kFloat, "fp32", {B, C, Ho, Wo});
+  seg_arg_ok("out_mask", out_mask, mt, mname, {B, Ho, Wo});
+  if (H * W > INT32_MAX || out_mask.numel() > INT32_MAX || C > INT32_MAX)
+    throw std::runtime_error("seg_aug_batch: an images plane and out_mask hold at most 2^31 - 1 pixels");
+  if (!std::isfinite(image_fill) || !std::isfinite(mask_fill))
+    throw std::runtime_error("seg_aug_batch: image_fill and mask_fill must be finite");
+  check(dlmpi_seg_aug_batch(ptr<float>(images), masks.data_ptr(), i64 ? 1 : 0, ptr<int64_t>(idx), ptr<int>(table),
+                            (int)B, (int)C, (int)H, (int)W, (int)Ho, (int)Wo, (float)image_fill, (float)mask_fill,
+                            (int64_t)std::llround(mask_fill), ptr<float>(out), out_mask.data_ptr(), cur_stream()),
+        "seg_aug_batch");
+}
+
 void register_ops(pybind11::module& m) {
   namespace py = pybind11;
   register_conv_fwd(m);
@@ -897,6 +938,7 @@ void register_ops(pybind11::module& m) {
         py::arg("go_numel") = -1);
   m.def("image_batch_mix", &image_batch_mix);
   m.def("mix_batch_", &mix_batch_);
+  m.def("seg_aug_batch", &seg_aug_batch);
   m.def("bce_fwd", &bce_fwd);
   m.def("bce_bwd", &bce_bwd);
   m.def("argmax_correct", &argmax_correct);

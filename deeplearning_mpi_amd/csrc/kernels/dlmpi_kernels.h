@@ -513,6 +513,13 @@ hipError_t dlmpi_image_batch_mix(const uint8_t* data, const int64_t* labels, con
 // in-place mix of a contiguous fp32 [B][C][H][W] batch; labels_b[b] = labels[B - 1 - b], lam_out[0] = lam
 hipError_t dlmpi_mix_batch(float* x, const int64_t* labels, int B, int C, int H, int W, int kind, float lam, int y0,
                            int y1, int x0, int x1, int64_t* labels_b, float* lam_out, hipStream_t s);
+// segmentation augmentation (seg_aug.hip): out[b] = bilinear, out_mask[b] = nearest resampling of sample idx[b]
+// through row idx[b] of `table` (int32 [N][6], the Q16 inverse affine map a b c d e f).  images [N][C][H][W] fp32,
+// masks [N][H][W] float (mask_i64 0, filled with mask_fill_f) or int64 (mask_i64 1, mask_fill_i) as out_mask
+// [B][Ho][Wo]; out [B][C][Ho][Wo] fp32.  H * W and B * Ho * Wo must fit an int.
+hipError_t dlmpi_seg_aug_batch(const float* images, const void* masks, int mask_i64, const int64_t* idx,
+                               const int* table, int B, int C, int H, int W, int Ho, int Wo, float image_fill,
+                               float mask_fill_f, int64_t mask_fill_i, float* out, void* out_mask, hipStream_t s);
 
 // fault injection: keep stream s busy for `ms` milliseconds (bounded; tests of the watchdog)
 hipError_t dlmpi_delay(double ms, hipStream_t s);

@@ -17,7 +17,10 @@ device-side gather:
 * :class:`DeviceCachedDataset` -- any deterministic map-style dataset (the reference UNet's
   image/mask dataset has no random augmentation) materialised once on the device; batches are
   ``index_select`` gathers.
-* :class:`DeviceBatches` -- iterates either in :class:`DistributedSampler` order (the epoch's index
+* :class:`DeviceSegDataset` -- the same image / mask pairs with geometric augmentation (flip, scale, rotate,
+  translate, crop; ``data/seg_aug.py``): a batch is ONE HIP kernel (``csrc/kernels/seg_aug.hip``) that gathers
+  and resamples image and mask through the sample's row of the epoch's parameter table.
+* :class:`DeviceBatches` -- iterates any of them in :class:`DistributedSampler` order (the epoch's index
   list goes to the device in one copy), optionally writing into fixed tensors so a captured
   hipGraph step can consume them without a copy.
 """
@@ -28,6 +31,7 @@ import torch
 
 from .datasets import CIFAR10, CIFAR_MEAN, CIFAR_STD
 from .mix import KINDS, MixConfig, draw_mix, mix_reference
+from .seg_aug import SegAugConfig, draw_seg_aug, seg_aug_reference
 
 _M32 = 0xFFFFFFFF
 
@@ -176,6 +180,89 @@ class DeviceCachedDataset:
         if self.keys is not None:
             return dict(zip(self.keys, vals))
         return vals[0] if len(vals) == 1 else tuple(vals)
+
+
+class DeviceSegDataset:
+    """``{'image', 'mask'}`` items (image fp32 [C, H, W]; mask [H, W], float32 or int64 class indices) stacked
+    once on ``device`` as :class:`DeviceCachedDataset` stacks them; ``batch`` gathers by index AND augments, one
+    kernel (``csrc/kernels/seg_aug.hip``): flip, scale, rotate, translate as ``aug`` says, bilinear for the image,
+    nearest for the mask (``data/seg_aug.py``), into ``out_size = (Ho, Wo)`` (default: the source size).  The
+    epoch's parameter table is drawn on the host and copied to the device when the epoch changes -- one small
+    copy per epoch, none per step.  Mask pixels from outside the source are ``mask_fill`` (default 0.0 for float
+    masks; int64 masks must name theirs, usually the loss's ignore_index).  On a CPU device ``batch`` runs
+    :func:`seg_aug_reference`."""
+
+    def __init__(self, dataset, device, aug: SegAugConfig, seed=0, out_size=None, mask_fill=None):
+        self.device = torch.device(device)
+        items = [dataset[i] for i in range(len(dataset))]
+        if not items:
+            raise ValueError("empty dataset")
+        if not (isinstance(items[0], dict) and "image" in items[0] and "mask" in items[0]):
+            raise ValueError("DeviceSegDataset takes a dataset of {'image', 'mask'} items")
+        self.keys = ["image", "mask"]
+        self.images = torch.stack([torch.as_tensor(it["image"]) for it in items]).to(self.device)
+        self.masks = torch.stack([torch.as_tensor(it["mask"]) for it in items]).to(self.device)
+        if self.images.dtype != torch.float32 or self.images.dim() != 4:
+            raise ValueError(f"images must be float32 [C, H, W], got {self.images.dtype} "
+                             f"{tuple(self.images.shape[1:])}")
+        self.N, self.C, self.H, self.W = self.images.shape
+        if self.masks.dtype not in (torch.float32, torch.int64) or tuple(self.masks.shape) != (self.N, self.H, self.W):
+            raise ValueError(f"masks must be float32 or int64 [{self.H}, {self.W}], got {self.masks.dtype} "
+                             f"{tuple(self.masks.shape[1:])}")
+        if not isinstance(aug, SegAugConfig):
+            raise TypeError("aug must be a SegAugConfig")
+        if mask_fill is None:
+            if self.masks.dtype == torch.int64:
+                raise ValueError("int64 masks have no default mask_fill: name one (the loss's ignore_index)")
+            mask_fill = 0.0
+        elif self.masks.dtype == torch.int64 and int(mask_fill) != mask_fill:
+            raise ValueError(f"mask_fill of int64 masks must be an integer, got {mask_fill}")
+        self.mask_fill = int(mask_fill) if self.masks.dtype == torch.int64 else float(mask_fill)
+        self.Ho, self.Wo = (self.H, self.W) if out_size is None else (int(out_size[0]), int(out_size[1]))
+        if self.Ho < 1 or self.Wo < 1:
+            raise ValueError(f"out_size must be at least (1, 1), got {out_size}")
+        self.aug, self.seed = aug, seed
+        self.redraws = 0                 # tables drawn (and copied to the device) so far
+        self._epoch = self._table = self._table_np = None
+        self._native = None
+        if self.device.type == "cuda":
+            from .._ext import native
+
+            self._native = native()
+
+    def __len__(self):
+        return self.N
+
+    def table(self, epoch: int) -> torch.Tensor:
+        """The parameter table of ``epoch`` on the device, int32 [N, 6]; redrawn when the epoch changes."""
+        if self._epoch != int(epoch):
+            self._table_np = draw_seg_aug(self.aug, self.seed, int(epoch), self.N, self.H, self.W, self.Ho, self.Wo)
+            self._table = torch.from_numpy(self._table_np).to(self.device)
+            self._epoch = int(epoch)
+            self.redraws += 1
+        return self._table
+
+    def batch(self, idx: torch.Tensor, epoch: int = 0, out=None):
+        """idx: int64 dataset indices on the device -> {'image': fp32 [B, C, Ho, Wo], 'mask': [B, Ho, Wo]},
+        written into ``out = (x, y)`` when given."""
+        B = idx.numel()
+        if out is None:
+            x = torch.empty(B, self.C, self.Ho, self.Wo, dtype=torch.float32, device=self.device)
+            y = torch.empty(B, self.Ho, self.Wo, dtype=self.masks.dtype, device=self.device)
+        else:
+            x, y = out
+            if tuple(x.shape) != (B, self.C, self.Ho, self.Wo) or tuple(y.shape) != (B, self.Ho, self.Wo):
+                raise ValueError(f"out must be ([{B}, {self.C}, {self.Ho}, {self.Wo}], [{B}, {self.Ho}, {self.Wo}]), "
+                                 f"got {tuple(x.shape)} and {tuple(y.shape)}")
+        table = self.table(epoch)
+        if self._native is not None:
+            self._native.seg_aug_batch(self.images, self.masks, idx, table, self.aug.image_fill, self.mask_fill, x, y)
+        else:
+            xr, yr = seg_aug_reference(self.images, self.masks, idx, self._table_np, self.Ho, self.Wo,
+                                       self.aug.image_fill, self.mask_fill)
+            x.copy_(xr)
+            y.copy_(yr)
+        return {"image": x, "mask": y}
 
 
 class DeviceBatches:
