@@ -1,6 +1,6 @@
 """Timings of the multi-class segmentation kernels at the UNet-512 head shape (M = 16 * 512^2 pixels).
 
-* head data gradient, C = 64, K = 2 and 4: the streaming kernel (bn.hip head_dgrad_bn_kernel) against the
+* head data gradient, C = 64, K = 2 and 4: the streaming kernel (head.hip head_dgrad_bn_kernel) against the
   GEMM path with the reduction padded to 8 -- the two sides of engine._HEAD_DGRAD -- alternated;
 * pixel-wise cross-entropy forward / backward, NHWC logits, K = 2 and 21: achieved GB/s over the bytes they
   must move (logits + labels + lse; + dlogits for the backward), beside bn_stats_kernel reading a bf16

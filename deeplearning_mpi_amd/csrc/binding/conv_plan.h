@@ -43,7 +43,7 @@ struct LastRan {
   int c16 = 0;           // conv2d_fwd: the 16-channel 4x4 stem kernel
   int convT_stream = 0;  // convT2x2_fwd: the streaming kernel
   int wgrad3 = 0;        // weight gradient: the 3x3 spatial-tile kernel
-  int head_dgrad = 0;    // data gradient of a <= 8-output 1x1 head: the streaming K = 2..4 kernel (bn.hip)
+  int head_dgrad = 0;    // data gradient of a <= 8-output 1x1 head: the streaming K = 2..4 kernel (head.hip)
 };
 extern Switches g_sw;
 extern LastRan g_ran;

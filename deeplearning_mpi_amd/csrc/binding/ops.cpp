@@ -22,7 +22,7 @@ namespace {
   throw std::runtime_error(std::string(what) + ": " + why);
 }
 
-// the chunked row reductions (bn.hip rowmap): 256 / (C / 8) row lanes per block
+// the chunked row reductions (rowreduce.h rowmap): 256 / (C / 8) row lanes per block
 void rowmap_shape(int64_t M, int C, const char* what) {
   if (C < 8 || C % 8 || C > 2048) bn_fail(what, "C must be a multiple of 8 in [8, 2048]");
   if (M < 1) bn_fail(what, "M < 1");
@@ -50,6 +50,18 @@ void floats_ok(const c10::optional<at::Tensor>& t, int64_t n, const char* what, 
   if (t.has_value() && t->defined()) floats_ok(*t, n, what, name);
 }
 bool given(const c10::optional<at::Tensor>& t) { return t.has_value() && t->defined(); }
+
+// the fused gradient producers (head.hip, pool.hip; row map of rowreduce.h): z and dx dense [M][C] of the activation
+// type, mscale / mshift per channel; -> their grid (partials [blocks][2][C])
+int fused_producer(int64_t M, int C, const at::Tensor& z, const at::Tensor& mscale, const at::Tensor& mshift,
+                   const at::Tensor& dx, const char* what) {
+  rowmap_shape(M, C, what);
+  slice_ok(z, M, C, C, 0, what, "z");
+  slice_ok(dx, M, C, C, 0, what, "dx");
+  floats_ok(mscale, C, what, "mscale");
+  floats_ok(mshift, C, what, "mshift");
+  return dlmpi_fused_blocks(M, C);
+}
 
 // the column reduce + finalize over partial [T][ns][C]
 void colsum_shape(const at::Tensor& partial, int T, int ns, int C, double count, const char* what) {
@@ -257,10 +269,7 @@ void maxpool_bwd(const at::Tensor& dy, const at::Tensor& idx, int N, int H, int 
 at::Tensor outer_dgrad_bn(const at::Tensor& dy, int lddy, int64_t M, int C, const at::Tensor& w, int ldw,
                           const at::Tensor& z, const at::Tensor& mscale, const at::Tensor& mshift, at::Tensor dx) {
   require_gpu(dy, "dy");
-  if (C < 8 || C % 8 || C > 2048 || M < 1)
-    throw std::runtime_error("outer_dgrad_bn: C a multiple of 8 in [8, 2048], M >= 1");
-  const int64_t rpb = 256 / (C / 8);
-  const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (M + rpb * 8 - 1) / (rpb * 8)));
+  const int nblk = fused_producer(M, C, z, mscale, mshift, dx, "outer_dgrad_bn");
   at::Tensor part = at::empty({nblk, 2, C}, dy.options().dtype(at::kFloat));
   same_type(dy, w, "outer_dgrad_bn w");
   same_type(dy, z, "outer_dgrad_bn z");
@@ -276,18 +285,14 @@ at::Tensor outer_dgrad_bn(const at::Tensor& dy, int lddy, int64_t M, int C, cons
 at::Tensor head_dgrad_bn(const at::Tensor& dl, int lddl, int K, int64_t M, int C, const at::Tensor& w, int ldw,
                          const at::Tensor& z, const at::Tensor& mscale, const at::Tensor& mshift, at::Tensor dx) {
   require_gpu(dl, "dl");
-  if (K < 2 || K > 4 || C < 8 || C % 8 || C > 2048 || M < 1 || lddl < K || ldw < K)
-    throw std::runtime_error("head_dgrad_bn: 2 <= K <= 4, C a multiple of 8 up to 2048, lddl / ldw >= K");
+  if (K < 2 || K > 4 || lddl < K || ldw < K) throw std::runtime_error("head_dgrad_bn: 2 <= K <= 4, lddl / ldw >= K");
+  const int nblk = fused_producer(M, C, z, mscale, mshift, dx, "head_dgrad_bn");
   same_type(dl, w, "head_dgrad_bn w");
   same_type(dl, z, "head_dgrad_bn z");
   same_type(dl, dx, "head_dgrad_bn dx");
-  if (dl.numel() < (M - 1) * lddl + K || w.numel() < (int64_t)(C - 1) * ldw + K || z.numel() < M * C ||
-      dx.numel() < M * C || mscale.numel() < C || mshift.numel() < C || mscale.scalar_type() != at::kFloat ||
-      mshift.scalar_type() != at::kFloat || !dl.is_contiguous() || !w.is_contiguous() || !z.is_contiguous() ||
-      !dx.is_contiguous())
+  if (dl.numel() < (M - 1) * lddl + K || w.numel() < (int64_t)(C - 1) * ldw + K || !dl.is_contiguous() ||
+      !w.is_contiguous() || !z.is_contiguous() || !dx.is_contiguous())
     throw std::runtime_error("head_dgrad_bn: operand sizes");
-  const int64_t rpb = 256 / (C / 8);
-  const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (M + rpb * 8 - 1) / (rpb * 8)));
   at::Tensor part = at::empty({nblk, 2, C}, dl.options().dtype(at::kFloat));
   check(dlmpi_head_dgrad_bn(dl.data_ptr(), lddl, K, M, C, w.data_ptr(), ldw, z.data_ptr(), ptr<float>(mscale),
                             ptr<float>(mshift), dx.data_ptr(), ptr<float>(part), nblk, act_f32(dl, "head_dgrad_bn"),
@@ -302,10 +307,11 @@ at::Tensor maxpool_bwd_bn(const at::Tensor& dy, const at::Tensor& idx, int N, in
                           int pad, int OH, int OW, const at::Tensor& z, const at::Tensor& mscale,
                           const at::Tensor& mshift, const c10::optional<at::Tensor>& add, int ldadd, int addoff,
                           at::Tensor dx) {
-  // more blocks than the generic reductions: every row is a latency-bound window gather
-  if (C < 8 || C % 8 || C > 2048) throw std::runtime_error("maxpool_bwd_bn: C a multiple of 8 in [8, 2048]");
-  const int64_t rpb = 256 / (C / 8);
-  const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(4096, ((int64_t)N * H * W + rpb * 8 - 1) / (rpb * 8)));
+  const int64_t M = (int64_t)N * H * W, MO = (int64_t)N * OH * OW;
+  const int nblk = fused_producer(M, C, z, mscale, mshift, dx, "maxpool_bwd_bn");
+  slice_ok(add, M, C, ldadd, addoff, "maxpool_bwd_bn", "add");
+  slice_ok(dy, MO, C, C, 0, "maxpool_bwd_bn", "dy");
+  slice_ok(idx, MO, C, C, 0, "maxpool_bwd_bn", "idx");
   at::Tensor part = at::empty({nblk, 2, C}, dy.options().dtype(at::kFloat));
   same_type(dy, z, "maxpool_bwd_bn z");
   same_type(dy, add, "maxpool_bwd_bn add");

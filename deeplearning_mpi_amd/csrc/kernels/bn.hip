@@ -11,236 +11,16 @@
 //   dyr = dy * [y > 0];  dbeta = sum dyr;  dgamma = sum dyr * xhat;
 //   dx  = k1*dyr + k2*x + k3   (k* folded per channel by the finalize kernel).
 // All tensors may be channel slices of a wider buffer (ld*, *off) so UNet's skip concat is free.
+#include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
+#include "rowreduce.h"
 #include "bnfin.h"
 
 namespace dlmpi {
 
-// ---------------- generic chunked row reduction layout --------------------------------------
-// A block of 256 threads walks rows; thread -> (chunk of 8 channels cc, row lane rr).
-struct RowMap {
-  int CC, RPB, cc, rr;
-  bool active;
-};
-__device__ __forceinline__ RowMap rowmap(int C) {
-  RowMap m;
-  m.CC = C >> 3;
-  m.RPB = 256 / m.CC;
-  m.cc = threadIdx.x % m.CC;
-  m.rr = threadIdx.x / m.CC;
-  m.active = m.rr < m.RPB;
-  return m;
-}
-
-// Block-level combine of per-thread [8] sums over threads that share a channel chunk; writes
-// partial[blk][k][C] for k < NS.
-// Fixed summation order over the row lanes -> bit-reproducible partials.
-template <int NS>
-__device__ void block_combine(float (*acc)[8], const RowMap& rm, int C, float* partial) {
-  __shared__ float buf[256 * NS * 8];
-#pragma unroll
-  for (int k = 0; k < NS; ++k)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) buf[(threadIdx.x * NS + k) * 8 + e] = acc[k][e];
-  __syncthreads();
-  for (int i = threadIdx.x; i < NS * C; i += 256) {
-    const int k = i / C, c = i - k * C, cc = c >> 3, e = c & 7;
-    float s = 0.f;
-    for (int r = 0; r < rm.RPB; ++r) s += buf[((r * rm.CC + cc) * NS + k) * 8 + e];
-    partial[(int64_t)blockIdx.x * NS * C + i] = s;
-  }
-}
-
-// Max-pool backward (gather, no atomics) fused with the BN-backward statistics of the BN+ReLU
-// that produced the pool input (the ResNet stem): dx = [z*scale + shift > 0] * sum of the window
-// gradients that selected the element, written as the masked gradient dyr, and per-block partials
-// {sum dyr, sum dyr*z} for the fused finalize (raw_z).  Replaces maxpool_bwd + bn_bwd_reduce and
-// the mask read of bn_bwd_apply.  `add` (optional): a second gradient of the pool input summed in
-// before the mask (the UNet encoder output also feeds the decoder's skip concat).
-// NWIN > 0: at most NWIN x NWIN windows hold an input pixel (ceil(k / stride): 2 for the ResNet
-// stem's 3x3/s2, 1 for the UNet's 2x2/s2); the candidate loop is unrolled with predication so all
-// window loads (index + gradient) are in flight at once instead of one dependent round trip per
-// window.  Same summation order as the generic loop (oh, then ow, ascending) -> identical results.
-template <int NWIN, typename T>
-__global__ __launch_bounds__(256) void maxpool_bwd_bn_kernel(const T* __restrict__ dy,
-                                                             const uint8_t* __restrict__ idx, int N, int H, int W,
-                                                             int C, int k, int stride, int pad, int OH, int OW,
-                                                             FastDiv fdW, FastDiv fdH, const T* __restrict__ z,
-                                                             const float* __restrict__ msc,
-                                                             const float* __restrict__ msh,
-                                                             const T* __restrict__ add, int ldadd, int addoff,
-                                                             T* __restrict__ dx, float* __restrict__ partial) {
-  const RowMap rm = rowmap(C);
-  float acc[2][8] = {};
-  const int64_t M = (int64_t)N * H * W;
-  if (rm.active) {
-    const int c0 = rm.cc * 8;
-    float sc[8], sh[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { sc[e] = msc[c0 + e]; sh[e] = msh[c0 + e]; }
-    for (int64_t row = (int64_t)blockIdx.x * rm.RPB + rm.rr; row < M; row += (int64_t)gridDim.x * rm.RPB) {
-      const uint32_t pix = (uint32_t)row;
-      const uint32_t t2 = fdiv(pix, fdW);
-      const int iw = (int)(pix - t2 * W);
-      const uint32_t n = fdiv(t2, fdH);
-      const int ih = (int)(t2 - n * H);
-      float g[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      int oh_lo = ih + pad - k + 1;
-      oh_lo = oh_lo <= 0 ? 0 : (oh_lo + stride - 1) / stride;
-      const int oh_hi = min((ih + pad) / stride, OH - 1);
-      int ow_lo = iw + pad - k + 1;
-      ow_lo = ow_lo <= 0 ? 0 : (ow_lo + stride - 1) / stride;
-      const int ow_hi = min((iw + pad) / stride, OW - 1);
-      if constexpr (NWIN > 0) {
-        uint64_t id[NWIN * NWIN];
-        typename Vec8<T>::type dv[NWIN * NWIN];
-#pragma unroll
-        for (int a = 0; a < NWIN; ++a)
-#pragma unroll
-          for (int b = 0; b < NWIN; ++b) {
-            const bool ok = oh_lo + a <= oh_hi && ow_lo + b <= ow_hi;
-            const int64_t op = ok ? ((int64_t)n * OH + oh_lo + a) * OW + ow_lo + b : 0;   // 0: a valid address
-            id[a * NWIN + b] = *reinterpret_cast<const uint64_t*>(idx + op * C + c0);
-            dv[a * NWIN + b] = raw8(dy + op * C + c0);
-          }
-#pragma unroll
-        for (int a = 0; a < NWIN; ++a)
-#pragma unroll
-          for (int b = 0; b < NWIN; ++b) {
-            const bool ok = oh_lo + a <= oh_hi && ow_lo + b <= ow_hi;
-            const int want = ok ? (ih - ((oh_lo + a) * stride - pad)) * k + (iw - ((ow_lo + b) * stride - pad)) : 256;
-            float d[8];
-            unpack8(dv[a * NWIN + b], d);
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-              if ((int)((id[a * NWIN + b] >> (8 * e)) & 0xff) == want) g[e] += d[e];
-          }
-      } else {
-        for (int oh = oh_lo; oh <= oh_hi; ++oh) {
-          for (int ow = ow_lo; ow <= ow_hi; ++ow) {
-            const uint8_t want = (uint8_t)((ih - (oh * stride - pad)) * k + (iw - (ow * stride - pad)));
-            const int64_t op = ((int64_t)n * OH + oh) * OW + ow;
-            const uint64_t id = *reinterpret_cast<const uint64_t*>(idx + op * C + c0);
-            float d[8];
-            load8(dy + op * C + c0, d);
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-              if (((id >> (8 * e)) & 0xff) == want) g[e] += d[e];
-          }
-        }
-      }
-      if (add) {   // second gradient source of the pool input (UNet: its skip-concat slice)
-        float a2[8];
-        load8(add + row * ldadd + addoff + c0, a2);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) g[e] += a2[e];
-      }
-      float zz[8];
-      load8(z + row * C + c0, zz);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) g[e] = zz[e] * sc[e] + sh[e] > 0.f ? g[e] : 0.f;
-      store8(dx + row * C + c0, g);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {   // statistics of the stored gradient
-        const float r = stored<T>(g[e]);
-        acc[0][e] += r;
-        acc[1][e] += r * zz[e];
-      }
-    }
-  }
-  block_combine<2>(acc, rm, C, partial);
-}
-
-// Data gradient of a 1x1 convolution with ONE output channel (the UNet head, reference
-// model.py:68) into the gradient of the BN+ReLU output below it: dx[m, c] = dy[m] * w[c] -- an
-// outer product, so a streaming kernel instead of a GEMM tile with 63 of 64 reduction lanes zero
-// -- masked by [z*scale + shift > 0], stored, and the BN-backward partials {sum dx, sum dx*z} per
-// block.  The bf16 x bf16 product is exact in fp32, as in the GEMM path: identical dx.
-template <typename T>
-__global__ __launch_bounds__(256) void outer_dgrad_bn_kernel(const T* __restrict__ dy, int lddy, int64_t M,
-                                                             int C, const T* __restrict__ w, int ldw,
-                                                             const T* __restrict__ z,
-                                                             const float* __restrict__ msc,
-                                                             const float* __restrict__ msh,
-                                                             T* __restrict__ dx, float* __restrict__ partial) {
-  const RowMap rm = rowmap(C);
-  float acc[2][8] = {};
-  if (rm.active) {
-    const int c0 = rm.cc * 8;
-    float wv[8], sc[8], sh[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      wv[e] = load1(w + (int64_t)(c0 + e) * ldw);
-      sc[e] = msc[c0 + e];
-      sh[e] = msh[c0 + e];
-    }
-    for (int64_t row = (int64_t)blockIdx.x * rm.RPB + rm.rr; row < M; row += (int64_t)gridDim.x * rm.RPB) {
-      const float d = load1(dy + row * lddy);
-      float zz[8], g[8];
-      load8(z + row * C + c0, zz);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) g[e] = zz[e] * sc[e] + sh[e] > 0.f ? d * wv[e] : 0.f;
-      store8(dx + row * C + c0, g);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float r = stored<T>(g[e]);
-        acc[0][e] += r;
-        acc[1][e] += r * zz[e];
-      }
-    }
-  }
-  block_combine<2>(acc, rm, C, partial);
-}
-
-// The same for a 1x1 convolution with K = 2..4 output channels (the multi-class UNet head):
-// dx[m, c] = [z*scale + shift > 0] * sum_k dl[m, k] * w[c, k], summed in fp32 in ascending k.  The GEMM
-// path pads the reduction from K to 8; here a row costs K broadcast loads of dl beside the z read and
-// the dx write.  Same row map, partial layout [blocks][2][C] and finalize as the K = 1 kernel.
-template <int K, typename T>
-__global__ __launch_bounds__(256) void head_dgrad_bn_kernel(const T* __restrict__ dl, int lddl, int64_t M, int C,
-                                                            const T* __restrict__ w, int ldw,
-                                                            const T* __restrict__ z,
-                                                            const float* __restrict__ msc,
-                                                            const float* __restrict__ msh,
-                                                            T* __restrict__ dx, float* __restrict__ partial) {
-  const RowMap rm = rowmap(C);
-  float acc[2][8] = {};
-  if (rm.active) {
-    const int c0 = rm.cc * 8;
-    float wv[K][8], sc[8], sh[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-#pragma unroll
-      for (int k = 0; k < K; ++k) wv[k][e] = load1(w + (int64_t)(c0 + e) * ldw + k);
-      sc[e] = msc[c0 + e];
-      sh[e] = msh[c0 + e];
-    }
-    for (int64_t row = (int64_t)blockIdx.x * rm.RPB + rm.rr; row < M; row += (int64_t)gridDim.x * rm.RPB) {
-      float d[K];
-#pragma unroll
-      for (int k = 0; k < K; ++k) d[k] = load1(dl + row * lddl + k);
-      float zz[8], g[8];
-      load8(z + row * C + c0, zz);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        float a = d[0] * wv[0][e];
-#pragma unroll
-        for (int k = 1; k < K; ++k) a += d[k] * wv[k][e];
-        g[e] = zz[e] * sc[e] + sh[e] > 0.f ? a : 0.f;
-      }
-      store8(dx + row * C + c0, g);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float r = stored<T>(g[e]);
-        acc[0][e] += r;
-        acc[1][e] += r * zz[e];
-      }
-    }
-  }
-  block_combine<2>(acc, rm, C, partial);
-}
+// the calling stream role's last-arriver tickets of colsum_fin_kernel (stream_roles.hip), 4096 ints
+int* fin_tickets(hipStream_t s);
 
 template <typename T>
 __global__ __launch_bounds__(256) void bn_stats_kernel(const T* __restrict__ x, int64_t M, int C, int ldx,
@@ -629,13 +409,6 @@ __global__ __launch_bounds__(256) void dual_dgrad_weights_kernel(const T* __rest
   if (threadIdx.x == 0) b[c] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-static inline unsigned ew_blocks(int64_t total) {
-  int64_t b = (total + 255) / 256;
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-
 }  // namespace dlmpi
 
 using namespace dlmpi;
@@ -651,106 +424,25 @@ extern "C" int dlmpi_reduce_blocks(int64_t M, int C) {
   return (int)b;
 }
 
-// Storage-type dispatch of the templated kernels: f32 = 1 -> float activations (fp32 precision
-// path), 0 -> bf16.  TA(p) casts a `const void*` / `void*` launcher argument to the chosen type.
-#define LAUNCH_TLAUNCH(KER, GRID, ...)                                               \
-  do {                                                                             \
-    if (f32) {                                                                     \
-      typedef float T;                                                             \
-      hipLaunchKernelGGL(KER<T>, GRID, dim3(256), 0, s, __VA_ARGS__);              \
-    } else {                                                                       \
-      typedef uint16_t T;                                                          \
-      hipLaunchKernelGGL(KER<T>, GRID, dim3(256), 0, s, __VA_ARGS__);              \
-    }                                                                              \
-  } while (0)
-#define CT(p) static_cast<const T*>(p)
-#define MT(p) static_cast<T*>(p)
+// Grid of the fused gradient producers (maxpool_bwd_bn, outer_dgrad_bn, head_dgrad_bn): twice the blocks of the plain reductions,
+// every row being a latency-bound gather or broadcast load.  0 as above.
+extern "C" int dlmpi_fused_blocks(int64_t M, int C) {
+  if (C < 8 || C % 8 || C > 2048 || M < 1) return 0;
+  const int64_t rpb = 256 / (C / 8);
+  return (int)std::max<int64_t>(1, std::min<int64_t>(4096, (M + rpb * 8 - 1) / (rpb * 8)));
+}
 
 extern "C" hipError_t dlmpi_bn_stats(const void* x, int64_t M, int C, int ldx, int xoff, float* partial, int nblk,
                                      int f32, hipStream_t s) {
   if (C < 8 || C % 8 || C > 2048 || M < 1 || nblk < 1) return hipErrorInvalidValue;
-  LAUNCH_TLAUNCH(bn_stats_kernel, dim3(nblk), CT(x), M, C, ldx, xoff, partial);
+  WITH_T(f32, hipLaunchKernelGGL(bn_stats_kernel<T>, dim3(nblk), dim3(256), 0, s, (const T*)x, M, C, ldx, xoff,
+                                 partial));
   return hipGetLastError();
 }
 
 extern "C" int dlmpi_colsum_ws_doubles(int T, int C) { return colsum_slices(T) * 2 * C; }
 
-// Self-resetting per-channel-group tickets of colsum_fin_kernel, one array per device, zeroed once
-// (the first use happens before any hipGraph capture: the warm-up steps run eagerly).
-// Last-arriver tickets of the fused finalize: one self-resetting array per device and stream
-// ROLE.  Launches on one stream are serialised, so they can share an array; the engine's auxiliary
-// streams (models/engine.py: the weight-gradient side stream and the residual-branch stream) run
-// colsum_fin launches concurrently with the main stream's, so each role gets its own array.
-// (Per role rather than per stream: a graph capture runs the main role on a fresh capture stream,
-// where no allocation may happen.)
-constexpr int kTicketRoles = 4;   // 0 = main (any unregistered stream), 1..3 = registered aux streams
-static int* g_tickets[64] = {};
-static hipStream_t g_aux_stream[64][kTicketRoles] = {};
-
-static int* tickets_for_device(int dev) {
-  if (!g_tickets[dev]) {
-    int* p = nullptr;
-    if (hipMalloc(&p, kTicketRoles * 4096 * sizeof(int)) != hipSuccess) return nullptr;
-    if (hipMemset(p, 0, kTicketRoles * 4096 * sizeof(int)) != hipSuccess) return nullptr;
-    g_tickets[dev] = p;
-  }
-  return g_tickets[dev];
-}
-
-static int* fin_tickets(hipStream_t s) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-  int* t = tickets_for_device(dev);
-  if (!t) return nullptr;
-  for (int r = 1; r < kTicketRoles; ++r)
-    if (s != nullptr && s == g_aux_stream[dev][r]) return t + r * 4096;
-  return t;
-}
-
-static int role_of(hipStream_t s, int dev) {
-  for (int r = 1; r < kTicketRoles; ++r)
-    if (s != nullptr && s == g_aux_stream[dev][r]) return r;
-  return 0;
-}
-
-// Split-K workspaces of the conv kernel (conv_igemm.hip), per device and stream role like the
-// finalize tickets.  The slab grows on demand outside graph captures (the eager warm-up steps
-// size it); inside a capture a too-small slab makes the launcher fall back to no split.
-static float* g_sk_slab[64][kTicketRoles] = {};
-static size_t g_sk_slab_floats[64][kTicketRoles] = {};
-static int* g_sk_tk[64][kTicketRoles] = {};
-constexpr int kSplitTickets = 4096;
-
-extern "C" float* dlmpi_splitk_slab(hipStream_t s, size_t floats) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-  const int r = role_of(s, dev);
-  if (g_sk_slab_floats[dev][r] >= floats) return g_sk_slab[dev][r];
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return nullptr;
-  // the old slab is never freed: a captured hipGraph may still reference it (a few MB, kept)
-  const size_t n = floats + floats / 2;   // head room
-  float* p = nullptr;
-  if (hipMalloc(&p, n * sizeof(float)) != hipSuccess) return nullptr;
-  g_sk_slab[dev][r] = p;
-  g_sk_slab_floats[dev][r] = n;
-  return p;
-}
-
-extern "C" int* dlmpi_splitk_tickets(hipStream_t s, int n) {
-  int dev = 0;
-  if (n > kSplitTickets || hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-  const int r = role_of(s, dev);
-  if (!g_sk_tk[dev][r]) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return nullptr;
-    int* p = nullptr;
-    if (hipMalloc(&p, kSplitTickets * sizeof(int)) != hipSuccess) return nullptr;
-    if (hipMemsetAsync(p, 0, kSplitTickets * sizeof(int), s) != hipSuccess) return nullptr;   // ordered before the kernel
-    g_sk_tk[dev][r] = p;
-  }
-  return g_sk_tk[dev][r];
-}
+constexpr int kEwMaxBlocks = 8192;   // grid cap of the elementwise kernels (bn_apply, bn_bwd_apply)
 
 static int colsum_direct_max() { return kDirectMaxT; }   // the kernel holds <= kDirectMaxT rows
 
@@ -770,50 +462,6 @@ static hipError_t colsum_finalize(const float* partial, int T, int C, int ns, in
     hipLaunchKernelGGL(finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, s, ws, S, C, f);
   }
   return hipGetLastError();
-}
-
-extern "C" hipError_t dlmpi_outer_dgrad_bn(const void* dy, int lddy, int64_t M, int C, const void* w, int ldw,
-                                         const void* z, const float* mscale, const float* mshift, void* dx,
-                                         float* partial, int nblk, int f32, hipStream_t s) {
-  if (C % 8 || C > 2048 || M <= 0) return hipErrorInvalidValue;
-  LAUNCH_TLAUNCH(outer_dgrad_bn_kernel, dim3(nblk), CT(dy), lddy, M, C, CT(w), ldw, CT(z), mscale, mshift, MT(dx),
-                partial);
-  return hipGetLastError();
-}
-
-// dl [M][lddl] (columns 0..K-1 read), w [C][ldw] (w[c][k] = the head weight of class k, channel c)
-extern "C" hipError_t dlmpi_head_dgrad_bn(const void* dl, int lddl, int K, int64_t M, int C, const void* w, int ldw,
-                                          const void* z, const float* mscale, const float* mshift, void* dx,
-                                          float* partial, int nblk, int f32, hipStream_t s) {
-  if (C % 8 || C > 2048 || M <= 0 || K < 2 || K > 4 || lddl < K || ldw < K || nblk < 1) return hipErrorInvalidValue;
-#define HEAD_DGRAD_K(K_)                                                                                     \
-  case K_:                                                                                                   \
-    if (f32)                                                                                                 \
-      hipLaunchKernelGGL((head_dgrad_bn_kernel<K_, float>), dim3(nblk), dim3(256), 0, s, (const float*)dl,   \
-                         lddl, M, C, (const float*)w, ldw, (const float*)z, mscale, mshift, (float*)dx,      \
-                         partial);                                                                           \
-    else                                                                                                     \
-      hipLaunchKernelGGL((head_dgrad_bn_kernel<K_, uint16_t>), dim3(nblk), dim3(256), 0, s,                  \
-                         (const uint16_t*)dl, lddl, M, C, (const uint16_t*)w, ldw, (const uint16_t*)z,       \
-                         mscale, mshift, (uint16_t*)dx, partial);                                            \
-    break;
-  switch (K) {
-    HEAD_DGRAD_K(2)
-    HEAD_DGRAD_K(3)
-    HEAD_DGRAD_K(4)
-  }
-#undef HEAD_DGRAD_K
-  return hipGetLastError();
-}
-
-extern "C" hipError_t dlmpi_set_aux_stream(hipStream_t s, int role) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64 || role < 1 || role >= kTicketRoles || !tickets_for_device(dev))
-    return hipErrorInvalidValue;   // (allocates outside any capture)
-  g_aux_stream[dev][role] = s;
-  return hipSuccess;
 }
 
 extern "C" hipError_t dlmpi_bn_finalize(const float* partial, int ntiles, int C, double count, const float* gamma,
@@ -842,8 +490,9 @@ extern "C" hipError_t dlmpi_bn_apply2(const void* x, int ldx, int xoff, int64_t 
                                       int f32, hipStream_t s) {
   if (C % 8 || ((rscale != nullptr) != (rshift != nullptr)) || (rscale && !res)) return hipErrorInvalidValue;
   const int64_t total = M * (C / 8);
-  LAUNCH_TLAUNCH(bn_apply_kernel, dim3(ew_blocks(total)), CT(x), ldx, xoff, M, C, make_fastdiv(C / 8), scale, shift,
-                CT(res), ldres, resoff, relu, MT(y), ldy, yoff, mbits, rscale, rshift);
+  WITH_T(f32, hipLaunchKernelGGL(bn_apply_kernel<T>, dim3(ew_blocks(total, kEwMaxBlocks)), dim3(256), 0, s,
+                                 (const T*)x, ldx, xoff, M, C, make_fastdiv(C / 8), scale, shift, (const T*)res, ldres,
+                                 resoff, relu, (T*)y, ldy, yoff, mbits, rscale, rshift));
   return hipGetLastError();
 }
 
@@ -859,8 +508,8 @@ extern "C" hipError_t dlmpi_bn_bwd_reduce(const void* dy, int lddy, int dyoff, c
                                           const float* mean, const float* invstd, float* partial, int nblk,
                                           int f32, hipStream_t s) {
   if (C < 8 || C % 8 || C > 2048 || M < 1 || nblk < 1 || (x && !(mean && invstd))) return hipErrorInvalidValue;
-  LAUNCH_TLAUNCH(bn_bwd_reduce_kernel, dim3(nblk), CT(dy), lddy, dyoff, CT(ymask), ldym, ymoff, CT(x), ldx, xoff, M, C,
-                mean, invstd, partial);
+  WITH_T(f32, hipLaunchKernelGGL(bn_bwd_reduce_kernel<T>, dim3(nblk), dim3(256), 0, s, (const T*)dy, lddy, dyoff,
+                                 (const T*)ymask, ldym, ymoff, (const T*)x, ldx, xoff, M, C, mean, invstd, partial));
   return hipGetLastError();
 }
 
@@ -893,16 +542,17 @@ extern "C" hipError_t dlmpi_bn_bwd_apply(const void* dy, int lddy, int dyoff, co
                                          const float* coef, void* dx, void* dyr_out, int f32, hipStream_t s) {
   if (C % 8) return hipErrorInvalidValue;
   const int64_t total = M * (C / 8);
-  LAUNCH_TLAUNCH(bn_bwd_apply_kernel, dim3(ew_blocks(total)), CT(dy), lddy, dyoff, CT(ymask), ldym, ymoff, CT(x), ldx,
-                xoff, M, C, make_fastdiv(C / 8), coef, MT(dx), MT(dyr_out));
+  WITH_T(f32, hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(ew_blocks(total, kEwMaxBlocks)), dim3(256), 0, s,
+                                 (const T*)dy, lddy, dyoff, (const T*)ymask, ldym, ymoff, (const T*)x, ldx, xoff, M, C,
+                                 make_fastdiv(C / 8), coef, (T*)dx, (T*)dyr_out));
   return hipGetLastError();
 }
-
 
 extern "C" hipError_t dlmpi_dual_dgrad_weights(const void* w, int C, int K, const float* coef, void* w2, float* b,
                                                int f32, hipStream_t s) {
   if (C <= 0 || K <= 0) return hipErrorInvalidValue;
-  LAUNCH_TLAUNCH(dual_dgrad_weights_kernel, dim3(C), CT(w), K, coef, MT(w2), b);
+  WITH_T(f32, hipLaunchKernelGGL(dual_dgrad_weights_kernel<T>, dim3(C), dim3(256), 0, s, (const T*)w, K, coef, (T*)w2,
+                                 b));
   return hipGetLastError();
 }
 
@@ -913,33 +563,4 @@ extern "C" hipError_t dlmpi_channel_sum(const void* x, int64_t M, int C, int ldx
   if (e != hipSuccess) return e;
   return dlmpi_bn_bwd_finalize(partial, nblk, C, (double)M, nullptr, nullptr, nullptr, nullptr, out_acc, nullptr, ws,
                                s);
-}
-
-extern "C" hipError_t dlmpi_maxpool_bwd_bn(const void* dy, const uint8_t* idx, int N, int H, int W, int C, int k,
-                                           int stride, int pad, int OH, int OW, const void* z, const float* mscale,
-                                           const float* mshift, const void* add, int ldadd, int addoff,
-                                           void* dx, float* partial, int nblk, int f32, hipStream_t s) {
-  if (C % 8 || C > 2048 || (int64_t)N * H * W >= (1ll << 31)) return hipErrorInvalidValue;
-  const int nw = (k + stride - 1) / stride;
-#define LAUNCH_MPB1(NW, T)                                                                                          \
-  hipLaunchKernelGGL((maxpool_bwd_bn_kernel<NW, T>), dim3(nblk), dim3(256), 0, s, CT(dy), idx, N, H, W, C, k, stride, \
-                     pad, OH, OW, make_fastdiv(W), make_fastdiv(H), CT(z), mscale, mshift, CT(add), ldadd, addoff,   \
-                     MT(dx), partial)
-#define LAUNCH_MPB(NW)          \
-  do {                         \
-    if (f32) {                 \
-      typedef float T;         \
-      LAUNCH_MPB1(NW, T);       \
-    } else {                   \
-      typedef uint16_t T;      \
-      LAUNCH_MPB1(NW, T);       \
-    }                          \
-  } while (0)
-  // fixed window extents for the 2x2/s2 and 3x3/s2 pools; NW 0: the general window loop
-  if (nw == 1) LAUNCH_MPB(1);
-  else if (nw == 2) LAUNCH_MPB(2);
-  else LAUNCH_MPB(0);
-#undef LAUNCH_MPB
-#undef LAUNCH_MPB1
-  return hipGetLastError();
 }

@@ -134,6 +134,27 @@ __device__ __forceinline__ void glds16_raw(const void* g, const char* lds) {
 }
 #pragma clang diagnostic pop
 
+// Grid of a grid-stride kernel over `total` items, one per thread of a 256-thread block: at most
+// `cap` blocks (each file's measured choice), at least one.
+static inline unsigned ew_blocks(int64_t total, int64_t cap) {
+  const int64_t b = (total + 255) / 256;
+  return (unsigned)(b > cap ? cap : (b < 1 ? 1 : b));
+}
+
+// Storage-type dispatch of the launchers of kernels templated on the activation type: runs the
+// statement(s) with T = float if f32 (the fp32 precision path), else T = uint16_t (bf16).  The
+// launchers' `const void*` / `void*` activations are cast inside: (const T*)x, (T*)y.
+#define WITH_T(f32, ...)   \
+  do {                     \
+    if (f32) {             \
+      typedef float T;     \
+      __VA_ARGS__;         \
+    } else {               \
+      typedef uint16_t T;  \
+      __VA_ARGS__;         \
+    }                      \
+  } while (0)
+
 // 4 KiB of zeros: out-of-bounds im2col / tile pieces load from here instead of branching
 // around the load (keeps the staging loads unconditional).
 static __device__ u32x4 g_zero_page[16] = {};

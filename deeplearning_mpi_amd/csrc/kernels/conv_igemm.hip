@@ -1289,7 +1289,7 @@ static hipError_t launch_tile(const ConvArgs* a, dim3 grid, hipStream_t s) {
 
 // Split-K plan for small grids (ResNet-18 on 32x32 CIFAR: layer4 is 1x1 pixels, 8 tiles x 72
 // K-steps): slices so that tiles x slices reaches ~256 blocks, >= 4 K-steps per slice, <= 8 slices.
-// Slabs (fp32) and tickets come per stream role (bn.hip), so the
+// Slabs (fp32) and tickets come per stream role (stream_roles.hip), so the
 // main and the branch stream can run split convolutions concurrently.
 static int splitk_plan(int tiles, int nk) {
   if (tiles >= 256 || nk < 8) return 1;

@@ -342,6 +342,8 @@ hipError_t dlmpi_dual_dgrad_weights(const void* w, int C, int K, const float* co
 hipError_t dlmpi_channel_sum(const void* x, int64_t M, int C, int ldx, int xoff, float* out_acc, float* partial,
                              int nblk, double* ws, int f32, hipStream_t s);
 int dlmpi_reduce_blocks(int64_t M, int C);
+// grid of the fused gradient producers (maxpool_bwd_bn, outer_dgrad_bn, head_dgrad_bn): partial [blocks][2][C]
+int dlmpi_fused_blocks(int64_t M, int C);
 
 // pooling / layout
 // scale/shift (optional): pool relu(x * scale + shift) (rounded to the storage type), i.e. BN-apply + ReLU fused
@@ -369,7 +371,7 @@ hipError_t dlmpi_head_dgrad_bn(const void* dl, int lddl, int K, int64_t M, int C
                                int nblk, int f32, hipStream_t s);
 // x [M][K] fp32 (a channels-last loss gradient) -> y [M][Kp] storage type, zero-padded (pixel_ce.hip)
 hipError_t dlmpi_nhwc_pad_cast(const float* x, int64_t M, int K, int Kp, void* y, int f32, hipStream_t s);
-// per-(device, stream role) split-K workspaces for the conv kernel (bn.hip): an fp32 slab of at least
+// per-(device, stream role) split-K workspaces for the conv kernel (stream_roles.hip): an fp32 slab of at least
 // `floats` elements and `n` zeroed self-resetting tickets; null if unavailable (e.g. would have to
 // grow during a graph capture)
 float* dlmpi_splitk_slab(hipStream_t s, size_t floats);

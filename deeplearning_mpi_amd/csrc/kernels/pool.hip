@@ -3,16 +3,12 @@
 // Replace ATen MaxPool2d (ResNet stem 3x3/s2/p1, UNet 2x2/s2: /root/reference/pytorch/unet/model.py:25),
 // AdaptiveAvgPool2d(1) (ResNet head), the host-side NCHW fp32 -> NHWC bf16 input conversion, and
 // nn.Upsample(scale_factor=2, mode='bilinear', align_corners=True) (model.py:39-40).
-#include "common.h"
+#include "rowreduce.h"
 
 namespace dlmpi {
 
-static inline unsigned ew_blocks(int64_t total) {
-  int64_t b = (total + 255) / 256;
-  if (b > 16384) b = 16384;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
+// grid of the elementwise kernels here: ew_blocks with this cap
+static inline dim3 pool_grid(int64_t total) { return dim3(ew_blocks(total, 16384)); }
 
 // Max pool forward; idx stores the winning window position (kh*k + kw) per channel, first max
 // in scan order wins (torch semantics).  Padding never wins.
@@ -194,6 +190,106 @@ __global__ void maxpool_bwd_kernel(const T* __restrict__ dy, const uint8_t* __re
     }
     store8(dx + pix * lddx + dxoff + cc * 8, g);
   }
+}
+
+// Max-pool backward (gather, no atomics) fused with the BN-backward statistics of the BN+ReLU
+// that produced the pool input (the ResNet stem): dx = [z*scale + shift > 0] * sum of the window
+// gradients that selected the element, written as the masked gradient dyr, and per-block partials
+// {sum dyr, sum dyr*z} for the fused finalize (raw_z).  Replaces maxpool_bwd + bn_bwd_reduce and
+// the mask read of bn_bwd_apply.  `add` (optional): a second gradient of the pool input summed in
+// before the mask (the UNet encoder output also feeds the decoder's skip concat).
+// NWIN > 0: at most NWIN x NWIN windows hold an input pixel (ceil(k / stride): 2 for the ResNet
+// stem's 3x3/s2, 1 for the UNet's 2x2/s2); the candidate loop is unrolled with predication so all
+// window loads (index + gradient) are in flight at once instead of one dependent round trip per
+// window.  Same summation order as the generic loop (oh, then ow, ascending) -> identical results.
+template <int NWIN, typename T>
+__global__ __launch_bounds__(256) void maxpool_bwd_bn_kernel(const T* __restrict__ dy,
+                                                             const uint8_t* __restrict__ idx, int N, int H, int W,
+                                                             int C, int k, int stride, int pad, int OH, int OW,
+                                                             FastDiv fdW, FastDiv fdH, const T* __restrict__ z,
+                                                             const float* __restrict__ msc,
+                                                             const float* __restrict__ msh,
+                                                             const T* __restrict__ add, int ldadd, int addoff,
+                                                             T* __restrict__ dx, float* __restrict__ partial) {
+  const RowMap rm = rowmap(C);
+  float acc[2][8] = {};
+  const int64_t M = (int64_t)N * H * W;
+  if (rm.active) {
+    const int c0 = rm.cc * 8;
+    float sc[8], sh[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { sc[e] = msc[c0 + e]; sh[e] = msh[c0 + e]; }
+    for (int64_t row = (int64_t)blockIdx.x * rm.RPB + rm.rr; row < M; row += (int64_t)gridDim.x * rm.RPB) {
+      const uint32_t pix = (uint32_t)row;
+      const uint32_t t2 = fdiv(pix, fdW);
+      const int iw = (int)(pix - t2 * W);
+      const uint32_t n = fdiv(t2, fdH);
+      const int ih = (int)(t2 - n * H);
+      float g[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      int oh_lo = ih + pad - k + 1;
+      oh_lo = oh_lo <= 0 ? 0 : (oh_lo + stride - 1) / stride;
+      const int oh_hi = min((ih + pad) / stride, OH - 1);
+      int ow_lo = iw + pad - k + 1;
+      ow_lo = ow_lo <= 0 ? 0 : (ow_lo + stride - 1) / stride;
+      const int ow_hi = min((iw + pad) / stride, OW - 1);
+      if constexpr (NWIN > 0) {
+        uint64_t id[NWIN * NWIN];
+        typename Vec8<T>::type dv[NWIN * NWIN];
+#pragma unroll
+        for (int a = 0; a < NWIN; ++a)
+#pragma unroll
+          for (int b = 0; b < NWIN; ++b) {
+            const bool ok = oh_lo + a <= oh_hi && ow_lo + b <= ow_hi;
+            const int64_t op = ok ? ((int64_t)n * OH + oh_lo + a) * OW + ow_lo + b : 0;   // 0: a valid address
+            id[a * NWIN + b] = *reinterpret_cast<const uint64_t*>(idx + op * C + c0);
+            dv[a * NWIN + b] = raw8(dy + op * C + c0);
+          }
+#pragma unroll
+        for (int a = 0; a < NWIN; ++a)
+#pragma unroll
+          for (int b = 0; b < NWIN; ++b) {
+            const bool ok = oh_lo + a <= oh_hi && ow_lo + b <= ow_hi;
+            const int want = ok ? (ih - ((oh_lo + a) * stride - pad)) * k + (iw - ((ow_lo + b) * stride - pad)) : 256;
+            float d[8];
+            unpack8(dv[a * NWIN + b], d);
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+              if ((int)((id[a * NWIN + b] >> (8 * e)) & 0xff) == want) g[e] += d[e];
+          }
+      } else {
+        for (int oh = oh_lo; oh <= oh_hi; ++oh) {
+          for (int ow = ow_lo; ow <= ow_hi; ++ow) {
+            const uint8_t want = (uint8_t)((ih - (oh * stride - pad)) * k + (iw - (ow * stride - pad)));
+            const int64_t op = ((int64_t)n * OH + oh) * OW + ow;
+            const uint64_t id = *reinterpret_cast<const uint64_t*>(idx + op * C + c0);
+            float d[8];
+            load8(dy + op * C + c0, d);
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+              if (((id >> (8 * e)) & 0xff) == want) g[e] += d[e];
+          }
+        }
+      }
+      if (add) {   // second gradient source of the pool input (UNet: its skip-concat slice)
+        float a2[8];
+        load8(add + row * ldadd + addoff + c0, a2);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) g[e] += a2[e];
+      }
+      float zz[8];
+      load8(z + row * C + c0, zz);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) g[e] = zz[e] * sc[e] + sh[e] > 0.f ? g[e] : 0.f;
+      store8(dx + row * C + c0, g);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {   // statistics of the stored gradient
+        const float r = stored<T>(g[e]);
+        acc[0][e] += r;
+        acc[1][e] += r * zz[e];
+      }
+    }
+  }
+  block_combine<2>(acc, rm, C, partial);
 }
 
 // Global average pool [N][HW][C] -> [N][C]
@@ -431,27 +527,16 @@ extern "C" hipError_t dlmpi_maxpool_fwd(const void* x, int N, int H, int W, int 
   const int64_t total = (int64_t)N * OH * OW * (C / 8);
   if (total >= (1ll << 31)) return hipErrorInvalidValue;
   const FastDiv a = make_fastdiv(C / 8), b = make_fastdiv(OW), c = make_fastdiv(OH);
-#define LAUNCH_MPF(K_, S_)                                                                                          \
-  do {                                                                                                            \
-    if (f32)                                                                                                      \
-      hipLaunchKernelGGL((maxpool_fwd_fixed_kernel<K_, S_, float>), dim3(ew_blocks(total)), dim3(256), 0, s,      \
-                         (const float*)x, N, H, W, C, ldx, xoff, pad, (float*)y, idx, OH, OW, scale, shift, a, b, c, \
-                         (float*)ys, ldys, ysoff);                                                                \
-    else                                                                                                          \
-      hipLaunchKernelGGL((maxpool_fwd_fixed_kernel<K_, S_, uint16_t>), dim3(ew_blocks(total)), dim3(256), 0, s,   \
-                         (const uint16_t*)x, N, H, W, C, ldx, xoff, pad, (uint16_t*)y, idx, OH, OW, scale, shift, a, \
-                         b, c, (uint16_t*)ys, ldys, ysoff);                                                       \
-    return hipGetLastError();                                                                                     \
-  } while (0)
+  const dim3 g = pool_grid(total);
+#define LAUNCH_MPF(K_, S_)                                                                                        \
+  WITH_T(f32, hipLaunchKernelGGL((maxpool_fwd_fixed_kernel<K_, S_, T>), g, dim3(256), 0, s, (const T*)x, N, H, W, C, \
+                                 ldx, xoff, pad, (T*)y, idx, OH, OW, scale, shift, a, b, c, (T*)ys, ldys, ysoff))
   if (k == 3 && stride == 2 && H > 0 && W > 0) LAUNCH_MPF(3, 2);
-  if (k == 2 && stride == 2 && H > 0 && W > 0) LAUNCH_MPF(2, 2);
-#undef LAUNCH_MPF
-  if (f32)
-    hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(ew_blocks(total)), dim3(256), 0, s, (const float*)x, N, H, W, C,
-                       ldx, xoff, k, stride, pad, (float*)y, idx, OH, OW, scale, shift, a, b, c);
+  else if (k == 2 && stride == 2 && H > 0 && W > 0) LAUNCH_MPF(2, 2);
   else
-    hipLaunchKernelGGL(maxpool_fwd_kernel<uint16_t>, dim3(ew_blocks(total)), dim3(256), 0, s, (const uint16_t*)x, N, H,
-                       W, C, ldx, xoff, k, stride, pad, (uint16_t*)y, idx, OH, OW, scale, shift, a, b, c);
+    WITH_T(f32, hipLaunchKernelGGL(maxpool_fwd_kernel<T>, g, dim3(256), 0, s, (const T*)x, N, H, W, C, ldx, xoff, k,
+                                   stride, pad, (T*)y, idx, OH, OW, scale, shift, a, b, c));
+#undef LAUNCH_MPF
   return hipGetLastError();
 }
 
@@ -460,72 +545,69 @@ extern "C" hipError_t dlmpi_maxpool_bwd(const void* dy, const uint8_t* idx, int 
                                         int addoff, void* dx, int lddx, int dxoff, int f32, hipStream_t s) {
   if (C % 8) return hipErrorInvalidValue;
   const int64_t total = (int64_t)N * H * W * (C / 8);
-  const dim3 g(ew_blocks(total));
-  if (f32)
-    hipLaunchKernelGGL(maxpool_bwd_kernel<float>, g, dim3(256), 0, s, (const float*)dy, idx, N, H, W, C, k, stride,
-                       pad, OH, OW, (const float*)add, ldadd, addoff, (float*)dx, lddx, dxoff, make_fastdiv(C / 8),
-                       make_fastdiv(W), make_fastdiv(H));
-  else
-    hipLaunchKernelGGL(maxpool_bwd_kernel<uint16_t>, g, dim3(256), 0, s, (const uint16_t*)dy, idx, N, H, W, C, k,
-                       stride, pad, OH, OW, (const uint16_t*)add, ldadd, addoff, (uint16_t*)dx, lddx, dxoff,
-                       make_fastdiv(C / 8), make_fastdiv(W), make_fastdiv(H));
+  WITH_T(f32, hipLaunchKernelGGL(maxpool_bwd_kernel<T>, pool_grid(total), dim3(256), 0, s, (const T*)dy, idx, N, H, W,
+                                 C, k, stride, pad, OH, OW, (const T*)add, ldadd, addoff, (T*)dx, lddx, dxoff,
+                                 make_fastdiv(C / 8), make_fastdiv(W), make_fastdiv(H)));
+  return hipGetLastError();
+}
+
+extern "C" hipError_t dlmpi_maxpool_bwd_bn(const void* dy, const uint8_t* idx, int N, int H, int W, int C, int k,
+                                           int stride, int pad, int OH, int OW, const void* z, const float* mscale,
+                                           const float* mshift, const void* add, int ldadd, int addoff,
+                                           void* dx, float* partial, int nblk, int f32, hipStream_t s) {
+  if (C % 8 || C > 2048 || (int64_t)N * H * W >= (1ll << 31)) return hipErrorInvalidValue;
+  const int nw = (k + stride - 1) / stride;
+#define LAUNCH_MPB(NW)                                                                                              \
+  WITH_T(f32, hipLaunchKernelGGL((maxpool_bwd_bn_kernel<NW, T>), dim3(nblk), dim3(256), 0, s, (const T*)dy, idx, N, H, \
+                                 W, C, k, stride, pad, OH, OW, make_fastdiv(W), make_fastdiv(H), (const T*)z, mscale, \
+                                 mshift, (const T*)add, ldadd, addoff, (T*)dx, partial))
+  // fixed window extents for the 2x2/s2 and 3x3/s2 pools; NW 0: the general window loop
+  if (nw == 1) LAUNCH_MPB(1);
+  else if (nw == 2) LAUNCH_MPB(2);
+  else LAUNCH_MPB(0);
+#undef LAUNCH_MPB
   return hipGetLastError();
 }
 
 extern "C" hipError_t dlmpi_avgpool_fwd(const void* x, int N, int HW, int C, void* y, int f32, hipStream_t s) {
-  const dim3 g(ew_blocks((int64_t)N * (C / 8)));
-  if (f32) hipLaunchKernelGGL(avgpool_fwd_kernel<float>, g, dim3(256), 0, s, (const float*)x, N, HW, C, (float*)y);
-  else hipLaunchKernelGGL(avgpool_fwd_kernel<uint16_t>, g, dim3(256), 0, s, (const uint16_t*)x, N, HW, C, (uint16_t*)y);
+  WITH_T(f32, hipLaunchKernelGGL(avgpool_fwd_kernel<T>, pool_grid((int64_t)N * (C / 8)), dim3(256), 0, s, (const T*)x,
+                                 N, HW, C, (T*)y));
   return hipGetLastError();
 }
 
 extern "C" hipError_t dlmpi_avgpool_bwd(const void* dy, int N, int HW, int C, void* dx, int f32, hipStream_t s) {
-  const dim3 g(ew_blocks((int64_t)N * HW * (C / 8)));
-  if (f32) hipLaunchKernelGGL(avgpool_bwd_kernel<float>, g, dim3(256), 0, s, (const float*)dy, N, HW, C, (float*)dx);
-  else hipLaunchKernelGGL(avgpool_bwd_kernel<uint16_t>, g, dim3(256), 0, s, (const uint16_t*)dy, N, HW, C,
-                          (uint16_t*)dx);
+  WITH_T(f32, hipLaunchKernelGGL(avgpool_bwd_kernel<T>, pool_grid((int64_t)N * HW * (C / 8)), dim3(256), 0, s,
+                                 (const T*)dy, N, HW, C, (T*)dx));
   return hipGetLastError();
 }
 
 extern "C" hipError_t dlmpi_nchw_to_nhwc(const float* x, int N, int C, int H, int W, int Cpad, void* y, int f32,
                                          hipStream_t s) {
   if (Cpad % 8 || Cpad < C) return hipErrorInvalidValue;
-  const dim3 g(ew_blocks((int64_t)N * H * W * (Cpad / 8)));
-  if (f32) hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, g, dim3(256), 0, s, x, N, C, H, W, Cpad, (float*)y);
-  else hipLaunchKernelGGL(nchw_to_nhwc_kernel<uint16_t>, g, dim3(256), 0, s, x, N, C, H, W, Cpad, (uint16_t*)y);
+  WITH_T(f32, hipLaunchKernelGGL(nchw_to_nhwc_kernel<T>, pool_grid((int64_t)N * H * W * (Cpad / 8)), dim3(256), 0, s,
+                                 x, N, C, H, W, Cpad, (T*)y));
   return hipGetLastError();
 }
 
 extern "C" hipError_t dlmpi_s2d_nchw(const float* x, int N, int C, int H, int W, int pad, int U, int V, int CS,
                                      void* y, int f32, hipStream_t s) {
   if ((4 * CS) % 8 || C > CS) return hipErrorInvalidValue;
-  const dim3 g(ew_blocks((int64_t)N * U * V * (CS / 2)));
-  if (f32) hipLaunchKernelGGL(s2d_nchw_kernel<float>, g, dim3(256), 0, s, x, N, C, H, W, pad, U, V, CS, (float*)y);
-  else hipLaunchKernelGGL(s2d_nchw_kernel<uint16_t>, g, dim3(256), 0, s, x, N, C, H, W, pad, U, V, CS, (uint16_t*)y);
+  WITH_T(f32, hipLaunchKernelGGL(s2d_nchw_kernel<T>, pool_grid((int64_t)N * U * V * (CS / 2)), dim3(256), 0, s, x, N,
+                                 C, H, W, pad, U, V, CS, (T*)y));
   return hipGetLastError();
 }
 
 extern "C" hipError_t dlmpi_upsample2x_fwd(const void* x, int N, int H, int W, int C, int ldx, int xoff, void* y,
                                            int ldy, int yoff, int f32, hipStream_t s) {
-  const dim3 g(ew_blocks((int64_t)N * 4 * H * W * (C / 8)));
-  if (f32)
-    hipLaunchKernelGGL(upsample2x_fwd_kernel<float>, g, dim3(256), 0, s, (const float*)x, N, H, W, C, ldx, xoff,
-                       (float*)y, ldy, yoff);
-  else
-    hipLaunchKernelGGL(upsample2x_fwd_kernel<uint16_t>, g, dim3(256), 0, s, (const uint16_t*)x, N, H, W, C, ldx, xoff,
-                       (uint16_t*)y, ldy, yoff);
+  WITH_T(f32, hipLaunchKernelGGL(upsample2x_fwd_kernel<T>, pool_grid((int64_t)N * 4 * H * W * (C / 8)), dim3(256), 0,
+                                 s, (const T*)x, N, H, W, C, ldx, xoff, (T*)y, ldy, yoff));
   return hipGetLastError();
 }
 
 extern "C" hipError_t dlmpi_upsample2x_bwd(const void* dy, int N, int H, int W, int C, int lddy, int dyoff, void* dx,
                                            int f32, hipStream_t s) {
   if (C % 8) return hipErrorInvalidValue;
-  const dim3 g(ew_blocks((int64_t)N * H * W * (C / 8)));
-  if (f32)
-    hipLaunchKernelGGL(upsample2x_bwd_kernel<float>, g, dim3(256), 0, s, (const float*)dy, N, H, W, C, lddy, dyoff,
-                       (float*)dx);
-  else
-    hipLaunchKernelGGL(upsample2x_bwd_kernel<uint16_t>, g, dim3(256), 0, s, (const uint16_t*)dy, N, H, W, C, lddy,
-                       dyoff, (uint16_t*)dx);
+  WITH_T(f32, hipLaunchKernelGGL(upsample2x_bwd_kernel<T>, pool_grid((int64_t)N * H * W * (C / 8)), dim3(256), 0, s,
+                                 (const T*)dy, N, H, W, C, lddy, dyoff, (T*)dx));
   return hipGetLastError();
 }

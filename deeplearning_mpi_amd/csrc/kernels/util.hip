@@ -33,12 +33,7 @@ __global__ __launch_bounds__(256) void gather_kernel(T* __restrict__ dst, const 
   }
 }
 
-static inline unsigned grid_for(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b > 4096) b = 4096;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
+static inline unsigned grid_for(int64_t n) { return ew_blocks(n, 4096); }
 
 }  // namespace dlmpi
 

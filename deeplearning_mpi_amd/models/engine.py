@@ -101,9 +101,9 @@ def record_on(stream, *objs):
 # Cross-stream buffer lifetimes are held by the issuing step (grad_side) rather than record_stream.
 _STREAM_HOLD = True
 
-# One-output-channel 1x1 data gradients as a streaming outer product (bn.hip outer_dgrad_bn_kernel).
+# One-output-channel 1x1 data gradients as a streaming outer product (head.hip outer_dgrad_bn_kernel).
 _OUTER_DGRAD = True
-# The same for 2..4 output channels (the multi-class UNet head, bn.hip head_dgrad_bn_kernel); False: the
+# The same for 2..4 output channels (the multi-class UNet head, head.hip head_dgrad_bn_kernel); False: the
 # GEMM data gradient with its reduction padded from K to 8 (A/B).
 _HEAD_DGRAD = True
 

@@ -38,7 +38,7 @@ def _new_aux_stream(idx, C, role):
 def _aux_stream(device, C, role):
     """Auxiliary streams, one per (device, role), shared by every backend instance: role 1 = the
     weight-gradient side stream, role 2 = the residual-branch stream.  The kernels keep a separate
-    last-arriver ticket array per role (bn.hip:fin_tickets)."""
+    last-arriver ticket array per role (stream_roles.hip:fin_tickets)."""
     idx = device.index if device.index is not None else torch.cuda.current_device()
     st = _AUX_STREAMS.get((idx, role))
     if st is None:

@@ -589,7 +589,14 @@ def _good_calls(C, M, T):
     sl = lambda p: {p: t(M, C), "ld" + p: C, p + "off": 0}    # noqa: E731
     no = lambda p: {p: None, "ld" + p: 0, p + "off": 0}       # noqa: E731
     fin = dict(gamma=f(C), mean=f(C), invstd=f(C), dgamma=f(C), dbeta=f(C), coef=f(3, C))
+    prod = lambda: dict(z=t(M, C), mscale=f(C), mshift=f(C))   # noqa: E731  (the fused gradient producers)
+    assert M == 10   # maxpool_bwd_bn below: a 1 x 2 x 5 input, 2x2 / s2 windows -> 1 x 1 x 2
     return {
+        "outer_dgrad_bn": dict(dy=t(M, 8), lddy=8, M=M, C=C, w=t(C * 8), ldw=8, **prod(), dx=t(M, C)),
+        "head_dgrad_bn": dict(dl=t(M, 8), lddl=8, K=3, M=M, C=C, w=t(C * 8), ldw=8, **prod(), dx=t(M, C)),
+        "maxpool_bwd_bn": dict(dy=t(2, C), idx=torch.zeros(2 * C, dtype=torch.uint8, device=DEV), N=1, H=2, W=5, C=C,
+                               k=2, stride=2, pad=0, OH=1, OW=2, **prod(), add=t(M, 2 * C), ldadd=2 * C, addoff=C,
+                               dx=t(M, C)),
         "bn_stats": dict(x=t(M, C), M=M, C=C, ldx=C, xoff=0, partial=f(1, 2, C), nblk=1),
         "channel_sum": dict(x=t(M, C), M=M, C=C, ldx=C, xoff=0, out=f(C)),
         "bn_finalize": dict(partial=f(T, 2, C), T=T, C=C, count=30.0, gamma=f(C), beta=f(C), running_mean=f(C),
@@ -657,6 +664,10 @@ def test_binders_reject_out_of_range_operands(nb):
                 bad.append((name, {p: t(M, C).float()}))                     # storage types differ
     bad += [("bn_bwd_apply", dict(dx=t(M - 1, C))), ("bn_bwd_apply", dict(dyr_out=t(M - 1, C))),
             ("bn_bwd_apply", dict(dx=t(M, C).float()))]
+    # the fused gradient producers: z / dx a row short, mscale a channel short; the pool's add slice past its row
+    for name in ("outer_dgrad_bn", "head_dgrad_bn", "maxpool_bwd_bn"):
+        bad += [(name, dict(z=t(M - 1, C))), (name, dict(dx=t(M - 1, C))), (name, dict(mscale=short))]
+    bad += [("maxpool_bwd_bn", dict(addoff=C + 8))]
 
     def call(name, over):
         a = dict(good[name])

@@ -1,4 +1,4 @@
-"""Data gradient of the K-class (K = 2..4) 1x1 UNet head as a streaming kernel (bn.hip
+"""Data gradient of the K-class (K = 2..4) 1x1 UNet head as a streaming kernel (head.hip
 head_dgrad_bn_kernel) against an fp64 reference on the same inputs: identical ReLU-mask decisions,
 every stored dx within one bf16 ulp of the rounded fp64 value, BN-backward partials equal to the sums
 of the stored dx; fp32 activations once; and a training UNet(out_classes=3) runs it.
