@@ -4,7 +4,13 @@ Flags keep the reference names and defaults: --num_epochs, --b
 process), --learning_rate, --random_seed, --model_dir, --model_filename, --resume.  Non-breaking
 additions: --arch, --num_classes, --synthetic, --data_root, --image_size, --backend, --device,
 --bucket_mb, --workers, --eval_every, --steps_per_epoch, --precision, --graph, --data_on_device,
---benchmark_steps, --label_smoothing, --mixup_alpha, --cutmix_alpha, --mix_prob, --mix_switch_prob.
+--benchmark_steps, --label_smoothing, --mixup_alpha, --cutmix_alpha, --mix_prob, --mix_switch_prob,
+--data_format, --rrc_scale, --rrc_ratio, --eval_crop, --norm.
+
+--data_format npy trains on a folder's images at any size: {data_root}/train_images.npy (uint8 [N, H, W, C]) and
+train_labels.npy (int64 [N]), val_* likewise (scripts/make_image_arrays.py writes them), live in device memory and
+one kernel per batch does gather + RandomResizedCrop(--image_size) + flip + normalize (data/rrc.py); evaluation
+is resize + centre crop (--eval_crop).
 
 Deliberate fixes of reference quirks (SURVEY.md §7.3): the sampler's epoch is advanced every epoch;
 evaluation runs on the unwrapped module (no stray rank-0-only collective, K8) with a non-augmenting
@@ -25,7 +31,8 @@ from torch.utils.data import DataLoader
 
 from .. import parallel
 from ..data import (CIFAR10, CifarTransform, DeviceBatches, DeviceImageDataset, DistributedSampler, MixConfig,
-                    SyntheticImages, draw_mix, mix_batch_)
+                    RrcConfig, SyntheticImages, draw_mix, mix_batch_)
+from ..data.datasets import CIFAR_MEAN, CIFAR_STD, IMAGENET_MEAN, IMAGENET_STD
 from ..models import ARCHS
 from ..ops import CrossEntropyLoss, backward, top1_correct
 from ..optim import LARS, SGD
@@ -72,7 +79,54 @@ def build_argparser(variant: str = "main") -> argparse.ArgumentParser:
                    help="time this many steps on a synthetic device batch, print images/sec and exit")
     add_layerwise_args(p, "sgd", "lars")
     add_recipe_args(p)
+    add_data_args(p)
     return p
+
+
+def add_data_args(p):
+    """Real images of any stored size, resampled to --image_size on the device (data/rrc.py)."""
+    p.add_argument("--data_format", default="cifar10", choices=["cifar10", "npy"],
+                   help="npy: {data_root}/{train,val}_images.npy + _labels.npy, kept in device memory and cropped / "
+                        "resized to --image_size by the batch kernel")
+    p.add_argument("--rrc_scale", type=float, nargs=2, default=[0.08, 1.0], metavar=("LO", "HI"),
+                   help="npy: area of the random crop as a fraction of the stored image")
+    p.add_argument("--rrc_ratio", type=float, nargs=2, default=[0.75, 1.3333], metavar=("LO", "HI"),
+                   help="npy: aspect ratio (w / h) of the random crop")
+    p.add_argument("--eval_crop", type=float, default=0.875,
+                   help="npy: evaluation resizes the centred square of this fraction of the shorter side")
+    p.add_argument("--norm", default=None, choices=["cifar", "imagenet"],
+                   help="normalisation constants (default: cifar for cifar10, imagenet for npy)")
+
+
+def check_data_args(parser, args):
+    if args.data_format != "npy":
+        return
+    if args.data_on_device == "0":
+        parser.error("--data_format npy lives on the device: it cannot run with --data_on_device 0")
+    if args.image_size < 1:
+        parser.error("--image_size must be at least 1")
+    if not (math.isfinite(args.eval_crop) and 0 < args.eval_crop <= 1):
+        parser.error("--eval_crop must lie in (0, 1]")
+    try:
+        rrc_config(args)
+    except ValueError as e:
+        parser.error(f"--rrc_scale / --rrc_ratio: {e}")
+
+
+def rrc_config(args) -> RrcConfig:
+    return RrcConfig(scale=tuple(args.rrc_scale), ratio=tuple(args.rrc_ratio))
+
+
+def norm_of(args):
+    """(mean, std) of --norm, which follows the data format when it is not given."""
+    name = getattr(args, "norm", None) or ("imagenet" if getattr(args, "data_format", "cifar10") == "npy" else "cifar")
+    return (IMAGENET_MEAN, IMAGENET_STD) if name == "imagenet" else (CIFAR_MEAN, CIFAR_STD)
+
+
+def input_side(args) -> int:
+    """The side of the step's input images: --image_size for synthetic and npy data, CIFAR's 32 otherwise."""
+    resized = getattr(args, "synthetic", False) or getattr(args, "data_format", "cifar10") == "npy"
+    return args.image_size if resized else 32
 
 
 def add_recipe_args(p):
@@ -142,8 +196,7 @@ def use_graph(args, device, pixels=None, comm_backend="single") -> bool:
     if device.type != "cuda" or comm_backend not in ("rccl", "single"):
         return False
     if pixels is None:
-        side = args.image_size if getattr(args, "synthetic", False) else 32
-        pixels = args.batch_size * side * side
+        pixels = args.batch_size * input_side(args) ** 2
     return pixels < int(os.environ.get("DLMPI_AUX_MIN_PIXELS", str(1 << 20)))
 
 
@@ -171,42 +224,39 @@ def evaluate(model, device, test_loader) -> float:
     return correct.item() / max(1, total)
 
 
-def run(args) -> dict:
-    comm = parallel.init_distributed(args.backend)
-    rank, world, local_rank = comm.rank, comm.world_size, comm.local_rank
-    device = comm.device if args.device == "auto" else torch.device(args.device)
-    set_random_seeds(args.random_seed)
-    model = ARCHS[args.arch](num_classes=args.num_classes).to(device)
-    model.precision = args.precision
-    ddp = parallel.DistributedDataParallel(model, bucket_cap_mb=args.bucket_mb)
-    model_filepath = os.path.join(args.model_dir, args.model_filename)
-    args.graph = use_graph(args, device, comm_backend=getattr(comm, "backend", "single"))
-
-    # the training step reads its batch from fixed tensors so that it can be captured (--graph)
-    x_static = torch.empty((args.batch_size, 3, args.image_size, args.image_size) if args.synthetic else
-                           (args.batch_size, 3, 32, 32), device=device)
-    y_static = torch.zeros(args.batch_size, dtype=torch.int64, device=device)
-    static = (x_static, y_static)
-    mix_cfg = recipe_of(args)
-    if mix_cfg is not None:   # the step reads a mixed target: (x, labels_a, labels_b, lam), all on the device
-        static += (torch.zeros_like(y_static), torch.ones(1, dtype=torch.float32, device=device))
-    on_device = (args.data_on_device == "1" or
+def build_loaders(args, device, static, mix_cfg):
+    """-> (train_set, sampler, train_loader, test_loader) of the run; ``static``: the captured step's inputs, which
+    a device-resident training loader fills in place under --graph."""
+    npy = getattr(args, "data_format", "cifar10") == "npy" and not args.synthetic
+    on_device = (npy or args.data_on_device == "1" or
                  (args.data_on_device == "auto" and device.type == "cuda" and not args.synthetic))
     test_bs = args.test_batch_size or args.batch_size
+    side = input_side(args)
+    mean, std = norm_of(args)
+    # the CIFAR loaders take their constants only when --norm names them: by default they are built as ever
+    norm = dict(mean=mean, std=std) if getattr(args, "norm", None) else {}
     if args.synthetic:
         shape = (3, args.image_size, args.image_size)
         train_set = SyntheticImages(args.synthetic_size, shape, args.num_classes, seed=1)
         test_set = SyntheticImages(max(64, args.synthetic_size // 8), shape, args.num_classes, seed=2)
+    elif npy:
+        # images of any stored size in HBM; one kernel per batch does gather + RandomResizedCrop + flip + normalize
+        # into [B, 3, S, S]; a mix is applied to the finished batch (step_inputs), as for any unmixed loader
+        train_set = DeviceImageDataset.from_npy(args.data_root, "train", device, mean=mean, std=std,
+                                                seed=args.random_seed, rrc=rrc_config(args), out_size=side)
+        test_set = DeviceImageDataset.from_npy(args.data_root, "val", device, mean=mean, std=std,
+                                               eval_crop=args.eval_crop, out_size=side)
     elif on_device:
         # the whole dataset in HBM; one kernel per batch does gather + crop/flip + normalize
-        train_set = DeviceImageDataset.cifar10(args.data_root, True, device, seed=args.random_seed, mix=mix_cfg)
-        test_set = DeviceImageDataset.cifar10(args.data_root, False, device, augment=False)
+        train_set = DeviceImageDataset.cifar10(args.data_root, True, device, seed=args.random_seed, mix=mix_cfg,
+                                               **norm)
+        test_set = DeviceImageDataset.cifar10(args.data_root, False, device, augment=False, **norm)
     else:
         # download=False semantics: the data must already be under data_root (see download.py)
         # augmentation = f(seed, epoch, index) (data/datasets.py SampleRng): rank-, worker- and
         # resume-independent
-        train_set = CIFAR10(args.data_root, train=True, transform=CifarTransform(True), seed=args.random_seed)
-        test_set = CIFAR10(args.data_root, train=False, transform=CifarTransform(False))
+        train_set = CIFAR10(args.data_root, train=True, transform=CifarTransform(True, **norm), seed=args.random_seed)
+        test_set = CIFAR10(args.data_root, train=False, transform=CifarTransform(False, **norm))
     sampler = DistributedSampler(train_set, seed=0)
     if on_device and not args.synthetic:
         train_loader = DeviceBatches(train_set, args.batch_size, sampler,
@@ -221,6 +271,29 @@ def run(args) -> dict:
         # state is the resume state every rank restores)
         test_loader = DataLoader(test_set, batch_size=test_bs, shuffle=False, num_workers=args.workers,
                                  pin_memory=pin, generator=torch.Generator().manual_seed(args.random_seed))
+    return train_set, sampler, train_loader, test_loader
+
+
+def run(args) -> dict:
+    comm = parallel.init_distributed(args.backend)
+    rank, world, local_rank = comm.rank, comm.world_size, comm.local_rank
+    device = comm.device if args.device == "auto" else torch.device(args.device)
+    set_random_seeds(args.random_seed)
+    model = ARCHS[args.arch](num_classes=args.num_classes).to(device)
+    model.precision = args.precision
+    ddp = parallel.DistributedDataParallel(model, bucket_cap_mb=args.bucket_mb)
+    model_filepath = os.path.join(args.model_dir, args.model_filename)
+    args.graph = use_graph(args, device, comm_backend=getattr(comm, "backend", "single"))
+
+    # the training step reads its batch from fixed tensors so that it can be captured (--graph)
+    side = input_side(args)
+    x_static = torch.empty((args.batch_size, 3, side, side), device=device)
+    y_static = torch.zeros(args.batch_size, dtype=torch.int64, device=device)
+    static = (x_static, y_static)
+    mix_cfg = recipe_of(args)
+    if mix_cfg is not None:   # the step reads a mixed target: (x, labels_a, labels_b, lam), all on the device
+        static += (torch.zeros_like(y_static), torch.ones(1, dtype=torch.float32, device=device))
+    train_set, sampler, train_loader, test_loader = build_loaders(args, device, static, mix_cfg)
     criterion = CrossEntropyLoss(label_smoothing=getattr(args, "label_smoothing", 0.0))
     if getattr(args, "optimizer", "sgd") == "lars":
         steps = args.benchmark_steps or args.num_epochs * (args.steps_per_epoch or len(train_loader))
@@ -353,4 +426,5 @@ def main(variant="main", argv=None):
     args = parser.parse_args(argv)
     check_layerwise_args(parser, args, "sgd")
     check_recipe_args(parser, args)
+    check_data_args(parser, args)
     return run(args)

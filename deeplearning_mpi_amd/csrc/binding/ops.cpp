@@ -1,7 +1,8 @@
 // Torch binding of the gfx950 kernel library outside the convolutions (conv_fwd.cpp, conv_bwd.cpp):
 // batch norm, pooling / layout, losses, optimisers, utilities and the device-resident input pipeline.
 // Every function launches on the current HIP stream and never synchronises, so a whole training
-// step can be captured into a hipGraph.
+// step can be captured into a hipGraph (the one exception, outside the step: image_rrc_batch reads a crop
+// table back the first time it sees it).
 #include "ops.h"
 
 #include <algorithm>
@@ -880,6 +881,83 @@ void seg_aug_batch(const at::Tensor& images, const at::Tensor& masks, const at::
         "seg_aug_batch");
 }
 
+// RandomResizedCrop batch (rrc.hip): data uint8 [N, H, W, C] gathered by idx [B], cropped to rows idx[b] of table
+// (int32 [N, 5]: top, left, h, w, flip), resized to out [B, C, Ho, Wo], flipped and normalised; labels gathered into
+// out_labels.  idx values are trusted.  The kernel reads whatever box the table names, so the WHOLE table is checked
+// here -- on the host, the one call of this file that synchronises -- the first time it is seen, once per epoch:
+// the checked tables are remembered by storage, version counter and geometry, and held so that their memory
+// cannot be handed to another tensor meanwhile.
+namespace {
+struct CheckedTable {
+  at::Tensor table;
+  const void* ptr;
+  uint32_t version;
+  int64_t H, W, Ho, Wo;
+};
+[[noreturn]] void rrc_fail(const std::string& why) { throw std::runtime_error("image_rrc_batch: " + why); }
+
+void rrc_table_ok(const at::Tensor& table, int64_t H, int64_t W, int64_t Ho, int64_t Wo) {
+  static std::vector<CheckedTable>* seen = new std::vector<CheckedTable>();   // (never destroyed: outlives HIP)
+  const uint32_t version = table._version();
+  for (const CheckedTable& c : *seen)
+    if (c.ptr == table.data_ptr() && c.version == version && c.table.is_alias_of(table) &&
+        c.table.sizes() == table.sizes() && c.H == H && c.W == W && c.Ho == Ho && c.Wo == Wo)
+      return;
+  const at::Tensor host = table.cpu();
+  const int* t = host.data_ptr<int>();
+  const int64_t cap = dlmpi_rrc_max_scale();
+  for (int64_t i = 0; i < host.size(0); ++i, t += 5) {
+    const int64_t top = t[0], left = t[1], h = t[2], w = t[3];
+    const std::string row = "table row " + std::to_string(i) + " (" + std::to_string(top) + ", " +
+                            std::to_string(left) + ", " + std::to_string(h) + ", " + std::to_string(w) + ", " +
+                            std::to_string(t[4]) + ")";
+    if (h < 1 || w < 1) rrc_fail(row + ": h and w must be at least 1");
+    if (top < 0 || left < 0 || top + h > H || left + w > W)
+      rrc_fail(row + ": the box does not lie inside the " + std::to_string(H) + " x " + std::to_string(W) + " image");
+    if (t[4] != 0 && t[4] != 1) rrc_fail(row + ": flip must be 0 or 1");
+    if (h > cap * Ho || w > cap * Wo)
+      rrc_fail(row + ": down-scaled by more than " + std::to_string(cap) + "x to " + std::to_string(Ho) + " x " +
+               std::to_string(Wo) + " (the weight table of the kernel holds 32 taps)");
+  }
+  if (seen->size() >= 4) seen->erase(seen->begin());   // a training and an evaluation table, with room to spare
+  seen->push_back({table, table.data_ptr(), version, H, W, Ho, Wo});
+}
+}  // namespace
+
+void image_rrc_batch(const at::Tensor& data, const at::Tensor& labels, const at::Tensor& idx, const at::Tensor& table,
+                     std::vector<double> mean, std::vector<double> sd, at::Tensor out, at::Tensor out_labels) {
+  if (!data.is_cuda() || !labels.is_cuda() || !idx.is_cuda() || !table.is_cuda() || !out.is_cuda() ||
+      !out_labels.is_cuda())
+    rrc_fail("every tensor must be on the GPU");
+  if (data.scalar_type() != at::kByte || labels.scalar_type() != at::kLong || idx.scalar_type() != at::kLong ||
+      table.scalar_type() != at::kInt || out.scalar_type() != at::kFloat || out_labels.scalar_type() != at::kLong)
+    rrc_fail("uint8 data, int64 labels and indices, an int32 table, fp32 output and int64 output labels");
+  if (!data.is_contiguous() || !labels.is_contiguous() || !idx.is_contiguous() || !table.is_contiguous() ||
+      !out.is_contiguous() || !out_labels.is_contiguous())
+    rrc_fail("every tensor must be contiguous");
+  if (data.dim() != 4 || data.numel() < 1) rrc_fail("data must be [N, H, W, C]");
+  const int64_t N = data.size(0), H = data.size(1), W = data.size(2), C = data.size(3);
+  if (C != 1 && C != 3) rrc_fail("C must be 1 or 3, got " + std::to_string(C));
+  if (mean.size() != (size_t)C || sd.size() != (size_t)C) rrc_fail("mean/std per channel");
+  if (labels.dim() != 1 || labels.size(0) != N) rrc_fail("labels must be [N]");
+  if (table.dim() != 2 || table.size(0) != N || table.size(1) != 5) rrc_fail("the table must be [N, 5]");
+  const int64_t B = idx.numel();
+  if (idx.dim() != 1 || B < 1 || B > 65535) rrc_fail("idx must be [B], 1 <= B <= 65535");
+  if (out.dim() != 4 || out.size(0) != B || out.size(1) != C || out.size(2) < 1 || out.size(3) < 1)
+    rrc_fail("out must be [B, C, Ho, Wo]");
+  if (out_labels.dim() != 1 || out_labels.size(0) != B) rrc_fail("out_labels must be [B]");
+  const int64_t Ho = out.size(2), Wo = out.size(3);
+  if (H > INT32_MAX / 4 || W > INT32_MAX / 4 || Ho > (1 << 20) || Wo > (1 << 20))
+    rrc_fail("image sides past the kernel's index range");
+  rrc_table_ok(table, H, W, Ho, Wo);
+  float m3[3] = {0.f, 0.f, 0.f}, s3[3] = {1.f, 1.f, 1.f};
+  for (int c = 0; c < C; ++c) { m3[c] = (float)mean[c]; s3[c] = (float)sd[c]; }
+  check(dlmpi_image_rrc_batch(ptr<uint8_t>(data), ptr<int64_t>(labels), ptr<int64_t>(idx), ptr<int>(table), (int)B,
+                              (int)H, (int)W, (int)C, (int)Ho, (int)Wo, m3, s3, ptr<float>(out),
+                              ptr<int64_t>(out_labels), cur_stream()),
+        "image_rrc_batch");
+}
+
 void register_ops(pybind11::module& m) {
   namespace py = pybind11;
   register_conv_fwd(m);
@@ -945,6 +1023,8 @@ void register_ops(pybind11::module& m) {
   m.def("image_batch_mix", &image_batch_mix);
   m.def("mix_batch_", &mix_batch_);
   m.def("seg_aug_batch", &seg_aug_batch);
+  m.def("image_rrc_batch", &image_rrc_batch);
+  m.def("rrc_max_scale", []() { return dlmpi_rrc_max_scale(); });
   m.def("bce_fwd", &bce_fwd);
   m.def("bce_bwd", &bce_bwd);
   m.def("argmax_correct", &argmax_correct);

@@ -522,6 +522,14 @@ hipError_t dlmpi_mix_batch(float* x, const int64_t* labels, int B, int C, int H,
 hipError_t dlmpi_seg_aug_batch(const float* images, const void* masks, int mask_i64, const int64_t* idx,
                                const int* table, int B, int C, int H, int W, int Ho, int Wo, float image_fill,
                                float mask_fill_f, int64_t mask_fill_i, float* out, void* out_mask, hipStream_t s);
+// RandomResizedCrop batch (rrc.hip): out[b] = normalize(flip(resize(crop(data[idx[b]])))) through row idx[b] of
+// `table` (int32 [N][5]: top, left, h, w, flip), anti-aliased bilinear; data [N][H][W][C] uint8 with C = 1 or 3,
+// out [B][C][Ho][Wo] fp32, out_labels[b] = labels[idx[b]].  The caller has checked that every box lies inside the
+// image and that h <= dlmpi_rrc_max_scale() * Ho, w likewise; B <= 65535.
+int dlmpi_rrc_max_scale();
+hipError_t dlmpi_image_rrc_batch(const uint8_t* data, const int64_t* labels, const int64_t* idx, const int* table,
+                                 int B, int H, int W, int C, int Ho, int Wo, const float* mean3, const float* std3,
+                                 float* out, int64_t* out_labels, hipStream_t s);
 
 // fault injection: keep stream s busy for `ms` milliseconds (bounded; tests of the watchdog)
 hipError_t dlmpi_delay(double ms, hipStream_t s);

@@ -5,3 +5,4 @@ from .device import (DeviceBatches, DeviceCachedDataset, DeviceImageDataset, Dev
                      image_batch_reference)
 from .mix import MixConfig, MixParams, draw_mix, mix_batch_, mix_reference  # noqa: F401
 from .seg_aug import SegAugConfig, draw_seg_aug, draw_seg_params, seg_affine, seg_aug_reference  # noqa: F401
+from .rrc import RrcConfig, center_box, draw_rrc, rrc_reference, rrc_taps, rrc_weights  # noqa: F401

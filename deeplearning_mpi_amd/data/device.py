@@ -14,6 +14,9 @@ device-side gather:
   rank count or worker count, and :func:`image_batch_reference` reproduces them exactly on the CPU.
   With ``mix=MixConfig(...)`` the same kernel also mixes the batch with itself (mixup / CutMix,
   ``data/mix.py``): "augment as today, then mix", and it writes ``labels_b`` and the device ``lam``.
+  With ``rrc=RrcConfig(...)`` or ``eval_crop=`` the batch is resampled to ``out_size`` instead
+  (RandomResizedCrop + flip, or resize + centre crop; ``data/rrc.py``, ``csrc/kernels/rrc.hip``), still ONE
+  kernel, through the sample's row of the epoch's crop table.
 * :class:`DeviceCachedDataset` -- any deterministic map-style dataset (the reference UNet's
   image/mask dataset has no random augmentation) materialised once on the device; batches are
   ``index_select`` gathers.
@@ -26,11 +29,15 @@ device-side gather:
 """
 from __future__ import annotations
 
+import os
+import warnings
+
 import numpy as np
 import torch
 
 from .datasets import CIFAR10, CIFAR_MEAN, CIFAR_STD
 from .mix import KINDS, MixConfig, draw_mix, mix_reference
+from .rrc import RrcConfig, center_box, draw_rrc, rrc_reference
 from .seg_aug import SegAugConfig, draw_seg_aug, seg_aug_reference
 
 _M32 = 0xFFFFFFFF
@@ -75,10 +82,17 @@ def image_batch_reference(data_hwc_u8: torch.Tensor, labels: torch.Tensor, idx: 
 
 class DeviceImageDataset:
     """uint8 images [N, H, W, C] + int64 labels resident on ``device``; ``batch`` assembles
-    normalised (optionally crop/flip-augmented) fp32 NCHW batches with one kernel."""
+    normalised (optionally crop/flip-augmented) fp32 NCHW batches with one kernel.
+
+    ``rrc`` (training: RandomResizedCrop + flip) or ``eval_crop`` (evaluation: the centred square of that fraction
+    of the shorter side) switch to the resampling kernel: batches are ``[B, C, *out_size]`` (default: the stored
+    size), cropped through the epoch's table (``data/rrc.py``), which is drawn on the host and copied to the device
+    when the epoch changes -- one small copy per epoch, none per step.  ``augment`` / ``pad`` then play no part,
+    and a mix is applied to the finished batch (``mix_batch_``), not here.  On a CPU device ``batch`` runs
+    :func:`rrc_reference`."""
 
     def __init__(self, images_hwc_u8, labels, device, augment=False, pad=4, mean=CIFAR_MEAN, std=CIFAR_STD, seed=0,
-                 mix: MixConfig = None):
+                 mix: MixConfig = None, rrc: RrcConfig = None, out_size=None, eval_crop=None):
         self.device = torch.device(device)
         self.data = torch.as_tensor(np.ascontiguousarray(images_hwc_u8)).to(self.device)
         self.labels = torch.as_tensor(np.asarray(labels, dtype=np.int64)).to(self.device)
@@ -87,6 +101,27 @@ class DeviceImageDataset:
         self.augment, self.pad, self.seed = augment, pad, seed
         self.mean, self.std = list(mean)[:self.C], list(std)[:self.C]
         self.mix = mix
+        self.rrc, self.eval_crop = rrc, eval_crop
+        self.resample = rrc is not None or eval_crop is not None
+        if self.resample:
+            if rrc is not None and eval_crop is not None:
+                raise ValueError("rrc (training) and eval_crop (evaluation) exclude each other")
+            if rrc is not None and not isinstance(rrc, RrcConfig):
+                raise TypeError("rrc must be an RrcConfig")
+            if mix is not None:
+                raise ValueError("a resampled batch is mixed after the batch kernel (mix_batch_), not by mix=")
+            if self.C not in (1, 3) or self.labels.shape != (self.N,):
+                raise ValueError("the resampling kernel takes 1 or 3 channels and one label per image")
+            size = (self.H, self.W) if out_size is None else out_size
+            self.Ho, self.Wo = (int(size), int(size)) if np.ndim(size) == 0 else (int(size[0]), int(size[1]))
+            if self.Ho < 1 or self.Wo < 1:
+                raise ValueError(f"out_size must be at least (1, 1), got {out_size}")
+            if eval_crop is not None:
+                self._fixed_box = center_box(self.H, self.W, float(eval_crop))
+            self.redraws = 0                 # tables drawn (and copied to the device) so far
+            self._epoch = self._table = self._table_np = None
+        elif out_size is not None:
+            raise ValueError("out_size needs rrc or eval_crop: the crop/flip pipeline keeps the stored size")
         self._native = None
         if self.device.type == "cuda":
             from .._ext import native
@@ -94,9 +129,36 @@ class DeviceImageDataset:
             self._native = native()
 
     @classmethod
-    def cifar10(cls, root, train, device, augment=None, seed=0, mix=None):
+    def cifar10(cls, root, train, device, augment=None, seed=0, mix=None, mean=CIFAR_MEAN, std=CIFAR_STD):
         data, targets = CIFAR10._load(root, train)
-        return cls(data, targets, device, augment=train if augment is None else augment, seed=seed, mix=mix)
+        return cls(data, targets, device, augment=train if augment is None else augment, mean=mean, std=std,
+                   seed=seed, mix=mix)
+
+    @classmethod
+    def from_npy(cls, root, split, device, **kwargs):
+        """``{root}/{split}_images.npy`` (uint8 [N, H, W, C]) and ``{split}_labels.npy`` (int64 [N]), as
+        ``scripts/make_image_arrays.py`` writes them; memory-mapped, so the host never holds a second copy."""
+        images = np.load(os.path.join(root, f"{split}_images.npy"), mmap_mode="r")
+        labels = np.load(os.path.join(root, f"{split}_labels.npy"), mmap_mode="r")
+        if images.dtype != np.uint8 or images.ndim != 4 or labels.shape != (images.shape[0],):
+            raise ValueError(f"{split}: images must be uint8 [N, H, W, C] with one label each, got {images.dtype} "
+                             f"{images.shape} and labels {labels.shape}")
+        with warnings.catch_warnings():   # torch warns that the map is read-only; the dataset never writes to it
+            warnings.filterwarnings("ignore", message="The given NumPy array is not writable")
+            return cls(images, labels, device, **kwargs)
+
+    def table(self, epoch: int) -> torch.Tensor:
+        """The crop table of ``epoch`` on the device, int32 [N, 5]; redrawn when the epoch changes (``rrc``), or the
+        one centre box for every sample and epoch (``eval_crop``)."""
+        if self._table is None or (self.rrc is not None and self._epoch != int(epoch)):
+            if self.rrc is not None:
+                self._table_np = draw_rrc(self.rrc, self.seed, int(epoch), self.N, self.H, self.W)
+            else:
+                self._table_np = np.ascontiguousarray(np.tile(np.array(self._fixed_box, dtype=np.int32), (self.N, 1)))
+            self._table = torch.from_numpy(self._table_np).to(self.device)
+            self._epoch = int(epoch)
+            self.redraws += 1
+        return self._table
 
     def __len__(self):
         return self.N
@@ -106,6 +168,8 @@ class DeviceImageDataset:
         (x, labels_a, labels_b [B] int64, lam [1] fp32), mixed as ``draw_mix(mix, seed, epoch, rank, batch_no)``
         says."""
         B = idx.numel()
+        if self.resample:
+            return self._resampled_batch(idx, epoch, out)
         if self.mix is not None:
             return self._mixed_batch(idx, epoch, out, batch_no, rank)
         if out is None:
@@ -119,6 +183,25 @@ class DeviceImageDataset:
         else:
             xr, yr = image_batch_reference(self.data, self.labels, idx, self.pad, self.augment, self.seed, epoch,
                                            self.mean, self.std)
+            x.copy_(xr)
+            y.copy_(yr)
+        return x, y
+
+    def _resampled_batch(self, idx, epoch, out):
+        B = idx.numel()
+        if out is None:
+            x = torch.empty(B, self.C, self.Ho, self.Wo, dtype=torch.float32, device=self.device)
+            y = torch.empty(B, dtype=torch.int64, device=self.device)
+        else:
+            x, y = out[:2]   # (the fixed tensors of a mixed step carry labels_b and lam behind these two)
+            if tuple(x.shape) != (B, self.C, self.Ho, self.Wo) or tuple(y.shape) != (B,):
+                raise ValueError(f"out must be ([{B}, {self.C}, {self.Ho}, {self.Wo}], [{B}]), got {tuple(x.shape)} "
+                                 f"and {tuple(y.shape)}")
+        table = self.table(epoch)
+        if self._native is not None:
+            self._native.image_rrc_batch(self.data, self.labels, idx, table, self.mean, self.std, x, y)
+        else:
+            xr, yr = rrc_reference(self.data, self.labels, idx, self._table_np, self.Ho, self.Wo, self.mean, self.std)
             x.copy_(xr)
             y.copy_(yr)
         return x, y
