@@ -8,6 +8,7 @@
 #include <string>
 
 #include "../kernels/dlmpi_kernels.h"
+#include "checks.h"
 #include "conv_plan.h"
 
 namespace dlmpi_ext {
@@ -25,7 +26,7 @@ static inline T* ptr(const at::Tensor& t) {
 }
 template <typename T>
 static inline T* optr(const c10::optional<at::Tensor>& t) {
-  return (t.has_value() && t->defined()) ? reinterpret_cast<T*>(t->data_ptr()) : nullptr;
+  return given(t) ? reinterpret_cast<T*>(t->data_ptr()) : nullptr;
 }
 
 static inline void require_gpu(const at::Tensor& t, const char* name) {
@@ -40,7 +41,7 @@ static inline int act_f32(const at::Tensor& t, const char* what) {
   throw std::runtime_error(std::string(what) + ": activations must be bf16 or fp32");
 }
 static inline void same_type(const at::Tensor& ref, const c10::optional<at::Tensor>& t, const char* what) {
-  if (t.has_value() && t->defined() && t->scalar_type() != ref.scalar_type())
+  if (given(t) && t->scalar_type() != ref.scalar_type())
     throw std::runtime_error(std::string(what) + ": operand dtype differs from the activations'");
 }
 static inline void same_type(const at::Tensor& ref, const at::Tensor& t, const char* what) {
@@ -49,7 +50,7 @@ static inline void same_type(const at::Tensor& ref, const at::Tensor& t, const c
 
 // The facts of a tensor argument the argument checks (conv_plan.h) work on; absent: numel -1.
 static inline int64_t onumel(const c10::optional<at::Tensor>& t) {
-  return (t.has_value() && t->defined()) ? (int64_t)t->numel() : -1;
+  return given(t) ? (int64_t)t->numel() : -1;
 }
 static inline Operand operand(const at::Tensor& t, int ld, int off) { return Operand{(int64_t)t.numel(), ld, off}; }
 static inline Operand operand(const c10::optional<at::Tensor>& t, int ld, int off) {
@@ -69,9 +70,17 @@ static inline void def_int(pybind11::module& m, const char* set, const char* get
   if (get) m.def(get, [v]() { return *v; });
 }
 
-// conv_fwd.cpp / conv_bwd.cpp: their Python functions
+// the Python functions of each translation unit (ops.cpp: register_ops calls them all)
 void register_conv_fwd(pybind11::module& m);
 void register_conv_bwd(pybind11::module& m);
+void register_bn(pybind11::module& m);
+void register_pool(pybind11::module& m);
+void register_loss(pybind11::module& m);
+void register_optim(pybind11::module& m);
+void register_data(pybind11::module& m);
+
+// bn.cpp: the shape of the chunked row reductions (rowreduce.h rowmap), shared with the fused producers of pool.cpp
+void rowmap_shape(int64_t M, int C, const char* fn);
 
 // ---- shared by the forward and data-gradient launches (conv_fwd.cpp) ----------------------------
 void finish_phase(dlmpi::ConvPhase& p, int Nimg, int C, int bm, bool f32 = false);

@@ -490,7 +490,7 @@ static inline int reduce_groups(int splits, int64_t total) {
   return (int)(G < 1 ? 1 : G);
 }
 
-// Batched split reduction (up to kWgradBatch weight gradients that became ready together; ops.cpp
+// Batched split reduction (up to kWgradBatch weight gradients that became ready together; conv_bwd.cpp
 // queues and flushes them): stage 1 -- a block per (entry with G > 0, 1024-float chunk, group g)
 // writes the group sum to ws2[g]; stage 2 -- a block per (entry, chunk) sums the G group sums (or,
 // G == 0, the splits themselves) in order and accumulates into the gradient.  The same sums in the

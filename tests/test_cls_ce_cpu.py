@@ -1,7 +1,7 @@
 """The classification cross-entropy with weight / ignore_index / label smoothing and two-label mixed targets
 (ops/losses.py cross_entropy on [N, K] logits), without a GPU: the closed form of RefBackend in fp64 against
 torch, the mixed-target identity, the corner cases, and the binder's argument rules through their integer-only
-binding (csrc/binding/ops.cpp check_cls_ce_args) -- one refused call per rule."""
+binding (csrc/binding/loss.cpp check_cls_ce_args) -- one refused call per rule."""
 import math
 
 import pytest
