@@ -11,7 +11,8 @@ namespace dlmpi {
 static inline dim3 pool_grid(int64_t total) { return dim3(ew_blocks(total, 16384)); }
 
 // Max pool forward; idx stores the winning window position (kh*k + kw) per channel, first max
-// in scan order wins (torch semantics).  Padding never wins.
+// in scan order wins (torch semantics).  Padding never wins: a window whose in-image taps are all -inf
+// reports its first in-image tap (the launcher refuses 2 * pad > k, so every window has one).
 // scale/shift (optional): the pooled input is relu(x * scale + shift) rounded to bf16, i.e. the
 // training-mode BN-apply + ReLU of the ResNet stem fused into the pool -- the stem's BN output is
 // never written or re-read (identical values and argmax to pooling the materialised bf16 tensor).
@@ -34,8 +35,10 @@ __global__ void maxpool_fwd_kernel(const T* __restrict__ x, int N, int H, int W,
     const int n = (int)n_;
     float best[8], sc[8], sh[8];
     uint8_t bi[8];
+    // the first in-image tap in scan order: what a window with no value above -inf reports (torch)
+    const uint8_t first = (uint8_t)(max(pad - oh * stride, 0) * k + max(pad - ow * stride, 0));
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { best[e] = -INFINITY; bi[e] = 0; }
+    for (int e = 0; e < 8; ++e) { best[e] = -INFINITY; bi[e] = first; }
     if (scale) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) { sc[e] = scale[cc * 8 + e]; sh[e] = shift[cc * 8 + e]; }
@@ -105,8 +108,9 @@ __global__ __launch_bounds__(256) void maxpool_fwd_fixed_kernel(const T* __restr
       }
     float best[8], sc[8], sh[8];
     uint8_t bi[8];
+    const uint8_t first = (uint8_t)(max(pad - oh * S, 0) * K + max(pad - ow * S, 0));   // as in maxpool_fwd_kernel
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { best[e] = -INFINITY; bi[e] = 0; }
+    for (int e = 0; e < 8; ++e) { best[e] = -INFINITY; bi[e] = first; }
     if (scale) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) { sc[e] = scale[cc * 8 + e]; sh[e] = shift[cc * 8 + e]; }
@@ -519,7 +523,9 @@ extern "C" hipError_t dlmpi_maxpool_fwd(const void* x, int N, int H, int W, int 
                                         int stride, int pad, void* y, uint8_t* idx, int OH, int OW,
                                         const float* scale, const float* shift, void* ys, int ldys, int ysoff,
                                         int f32, hipStream_t s) {
-  if (C % 8) return hipErrorInvalidValue;
+  if (C < 8 || C % 8) return hipErrorInvalidValue;
+  // idx is one byte per element (k * k - 1 <= 255); 2 * pad > k would leave a window wholly in padding
+  if (k < 1 || k > 16 || stride < 1 || pad < 0 || 2 * pad > k) return hipErrorInvalidValue;
   // ys: K == S, no padding, the windows tile the input exactly, an applied input (scale / shift)
   if (ys && (!scale || !shift || k != 2 || stride != 2 || pad != 0 || H != 2 * OH || W != 2 * OW || ldys % 8 ||
              ysoff % 8))
@@ -570,12 +576,14 @@ extern "C" hipError_t dlmpi_maxpool_bwd_bn(const void* dy, const uint8_t* idx, i
 }
 
 extern "C" hipError_t dlmpi_avgpool_fwd(const void* x, int N, int HW, int C, void* y, int f32, hipStream_t s) {
+  if (C < 8 || C % 8 || HW < 1) return hipErrorInvalidValue;
   WITH_T(f32, hipLaunchKernelGGL(avgpool_fwd_kernel<T>, pool_grid((int64_t)N * (C / 8)), dim3(256), 0, s, (const T*)x,
                                  N, HW, C, (T*)y));
   return hipGetLastError();
 }
 
 extern "C" hipError_t dlmpi_avgpool_bwd(const void* dy, int N, int HW, int C, void* dx, int f32, hipStream_t s) {
+  if (C < 8 || C % 8 || HW < 1) return hipErrorInvalidValue;
   WITH_T(f32, hipLaunchKernelGGL(avgpool_bwd_kernel<T>, pool_grid((int64_t)N * HW * (C / 8)), dim3(256), 0, s,
                                  (const T*)dy, N, HW, C, (T*)dx));
   return hipGetLastError();
@@ -599,6 +607,7 @@ extern "C" hipError_t dlmpi_s2d_nchw(const float* x, int N, int C, int H, int W,
 
 extern "C" hipError_t dlmpi_upsample2x_fwd(const void* x, int N, int H, int W, int C, int ldx, int xoff, void* y,
                                            int ldy, int yoff, int f32, hipStream_t s) {
+  if (C < 8 || C % 8 || H < 1 || W < 1) return hipErrorInvalidValue;
   WITH_T(f32, hipLaunchKernelGGL(upsample2x_fwd_kernel<T>, pool_grid((int64_t)N * 4 * H * W * (C / 8)), dim3(256), 0,
                                  s, (const T*)x, N, H, W, C, ldx, xoff, (T*)y, ldy, yoff));
   return hipGetLastError();
