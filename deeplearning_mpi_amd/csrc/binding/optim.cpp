@@ -17,8 +17,8 @@ void sgd_step(at::Tensor p, const at::Tensor& g, at::Tensor m, double lr, double
 void adam_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v, double lr, double b1, double b2,
                double eps, double wd, bool adamw, double bc1, double bc2, const c10::optional<at::Tensor>& clip,
                const c10::optional<at::Tensor>& tstep, bool clip_writeback) {
-  check(dlmpi_adam(ptr<float>(p), ptr<float>(g), ptr<float>(m), ptr<float>(v), p.numel(), (float)lr, (float)b1,
-                   (float)b2, (float)eps, (float)wd, adamw ? 1 : 0, (float)bc1, (float)bc2, optr<float>(clip),
+  check(dlmpi_adam(ptr<float>(p), ptr<float>(g), ptr<float>(m), ptr<float>(v), p.numel(), (float)lr, b1, b2,
+                   (float)eps, (float)wd, adamw ? 1 : 0, (float)bc1, (float)bc2, optr<float>(clip),
                    optr<float>(tstep), clip_writeback ? 1 : 0, cur_stream()),   // tstep advanced in place unless skipped
         "adam");
 }

@@ -9,6 +9,21 @@
 
 namespace dlmpi {
 
+// One element of the SGD update.  Every fusion is written out and contraction is off for the rest, so the
+// 16-byte loop and the element loop below round alike (bit-identical results): left to the compiler, the
+// element loop packed momentum * m and (1 - dampening) * g into one two-wide multiply and added them
+// unfused, while the 16-byte loop fused the second product into the sum.
+__device__ __forceinline__ void sgd_elem(float& p, float g, float& m, float lr, float momentum, float dampening,
+                                         float wd, int nesterov, int first, bool store_m) {
+#pragma clang fp contract(off)
+  if (wd != 0.f) g = __builtin_fmaf(wd, p, g);
+  if (store_m) {
+    m = first ? g : __builtin_fmaf(1.f - dampening, g, momentum * m);
+    g = nesterov ? __builtin_fmaf(momentum, m, g) : m;
+  }
+  p = __builtin_fmaf(-lr, g, p);
+}
+
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                   float* __restrict__ m, int64_t n, float lr, float momentum,
                                                   float dampening, float wd, int nesterov, int first,
@@ -16,41 +31,44 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
   if (skip_flag && *skip_flag != 0.f) return;
   // 16-byte accesses when every buffer allows them (the arena's do), else the element loop below
   const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m) & 15) == 0;
+  const bool mom = momentum != 0.f;   // without momentum m is neither read nor written (it may alias p)
   const int64_t n4 = vec ? n >> 2 : 0;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += stride) {
-    f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
-    f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
-    if (wd != 0.f) gv += wd * pv;
-    if (momentum != 0.f) {
-      f32x4 mv = first ? gv : momentum * reinterpret_cast<f32x4*>(m)[i] + (1.f - dampening) * gv;
-      reinterpret_cast<f32x4*>(m)[i] = mv;
-      gv = nesterov ? gv + momentum * mv : mv;
+    f32x4 pv = reinterpret_cast<f32x4*>(p)[i], mv = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+    if (mom && !first) mv = reinterpret_cast<f32x4*>(m)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float pe = pv[e], me = mv[e];
+      sgd_elem(pe, gv[e], me, lr, momentum, dampening, wd, nesterov, first, mom);
+      pv[e] = pe;
+      mv[e] = me;
     }
-    reinterpret_cast<f32x4*>(p)[i] = pv - lr * gv;
+    if (mom) reinterpret_cast<f32x4*>(m)[i] = mv;
+    reinterpret_cast<f32x4*>(p)[i] = pv;
   }
   // tail (or everything, unaligned)
   for (int64_t t = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += stride) {
-    float pv = p[t], gv = g[t];
-    if (wd != 0.f) gv += wd * pv;
-    if (momentum != 0.f) {
-      const float mv = first ? gv : momentum * m[t] + (1.f - dampening) * gv;
-      m[t] = mv;
-      gv = nesterov ? gv + momentum * mv : mv;
-    }
-    p[t] = pv - lr * gv;
+    float pv = p[t], mv = (mom && !first) ? m[t] : 0.f;
+    sgd_elem(pv, g[t], mv, lr, momentum, dampening, wd, nesterov, first, mom);
+    if (mom) m[t] = mv;
+    p[t] = pv;
   }
 }
 
 __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float lr, float b1, float b2,
                                           float eps, float wd, int adamw, float bc1, float bc2, float coef) {
+  // every fusion written out, contraction off for the rest: the element loop rounds as the 16-byte loop does
+  // (left to the compiler it packed v * b2 and (1 - b2) * g * g into one two-wide multiply and added them unfused)
+#pragma clang fp contract(off)
   g *= coef;
   if (wd != 0.f) {
-    if (adamw) p *= (1.f - lr * wd);
-    else g += wd * p;
+    if (adamw) p *= __builtin_fmaf(-lr, wd, 1.f);
+    else g = __builtin_fmaf(wd, p, g);
   }
   m += (g - m) * (1.f - b1);             // torch: exp_avg.lerp_(grad, 1 - beta1)
-  v = v * b2 + (1.f - b2) * g * g;
+  v = __builtin_fmaf(v, b2, (1.f - b2) * g * g);
   const float denom = sqrtf(v) / sqrtf(bc2) + eps;
   p -= (lr / bc1) * m / denom;
 }
@@ -63,18 +81,31 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
                                                    float b1, float b2, float eps, float wd, int adamw, float bc1,
                                                    float bc2, const float* __restrict__ clip_coef,
-                                                   const float* __restrict__ tstep, int wb) {
+                                                   const float* __restrict__ tstep, int wb, double b1d, double b2d) {
   // tstep = number of updates applied so far (device scalar): this update is number tstep + 1
   const float coef = clip_coef ? clip_coef[0] : 1.f;
   if (clip_coef && clip_coef[1] != 0.f) return;   // non-finite gradient norm: collective skip
   const bool store_g = wb && coef != 1.f;
   if (tstep) {   // step count on the device: bias corrections stay correct under hipGraph replay
-    const float t = *tstep + 1.f;
-    bc1 = 1.f - powf(b1, t);
-    bc2 = 1.f - powf(b2, t);
+    // 1 - beta^t from the caller's double betas, in fp64, rounded once (as lw_bias_corrections of
+    // optim_layerwise.hip): 1 - 0.999f is already 1.3e-5 off, and so was bc2 for the first thousand updates.
+    // t is a whole number, so beta^t is a square-and-multiply product (at most 2 x 32 fp64 multiplications,
+    // relative error below t 2^-52, which leaves 1 - beta^t exact to 2^-52 / (1 - beta)): every thread
+    // computes it, and two calls of pow() here cost the 25 M-element update 3 % of its time
+    double r1 = 1.0, r2 = 1.0, a1 = b1d, a2 = b2d;
+    for (uint32_t e = (uint32_t)(*tstep + 1.f); e; e >>= 1) {
+      if (e & 1) {
+        r1 *= a1;
+        r2 *= a2;
+      }
+      a1 *= a1;
+      a2 *= a2;
+    }
+    bc1 = (float)(1.0 - r1);
+    bc2 = (float)(1.0 - r2);
   }
-  // 16-byte accesses when every state array is aligned (the flat arenas are), scalar tail; the
-  // per-element arithmetic is unchanged (bit-identical)
+  // 16-byte accesses when every state array is aligned (the flat arenas are), scalar tail; both go through
+  // adam_elem, whose roundings are fixed in the source (bit-identical)
   const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0;
   const int64_t n4 = vec ? n / 4 : 0;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -201,11 +232,12 @@ extern "C" hipError_t dlmpi_sgd(float* p, const float* g, float* m, int64_t n, f
                      wd, nesterov, first, skip_flag);
   return hipGetLastError();
 }
-extern "C" hipError_t dlmpi_adam(float* p, float* g, float* m, float* v, int64_t n, float lr, float b1, float b2,
+// b1, b2 as doubles: the moment updates use their fp32 roundings, the device-side bias corrections the doubles
+extern "C" hipError_t dlmpi_adam(float* p, float* g, float* m, float* v, int64_t n, float lr, double b1, double b2,
                                  float eps, float wd, int adamw, float bc1, float bc2, const float* clip_coef,
                                  float* tstep, int wb, hipStream_t s) {
-  hipLaunchKernelGGL(adam_kernel, dim3(blocks_for(n / 4 + 1)), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps, wd, adamw,
-                     bc1, bc2, clip_coef, tstep, wb);
+  hipLaunchKernelGGL(adam_kernel, dim3(blocks_for(n / 4 + 1)), dim3(256), 0, s, p, g, m, v, n, lr, (float)b1, (float)b2,
+                     eps, wd, adamw, bc1, bc2, clip_coef, tstep, wb, b1, b2);
   if (tstep) hipLaunchKernelGGL(adam_step_advance_kernel, dim3(1), dim3(64), 0, s, tstep, clip_coef);
   return hipGetLastError();
 }

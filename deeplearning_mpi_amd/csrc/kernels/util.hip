@@ -28,8 +28,9 @@ __global__ __launch_bounds__(256) void gather_kernel(T* __restrict__ dst, const 
                                                      const int64_t* __restrict__ idx, int64_t n) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t j = idx[i];
-    if constexpr (ACC) dst[i] += src[j];
-    else dst[i] = j >= 0 ? src[j] : T(0);   // idx < 0: zero padding
+    const T v = j >= 0 ? src[j] : T(0);   // idx < 0: zero padding, in both variants
+    if constexpr (ACC) dst[i] += v;
+    else dst[i] = v;
   }
 }
 
