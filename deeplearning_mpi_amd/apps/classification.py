@@ -5,7 +5,7 @@ process), --learning_rate, --random_seed, --model_dir, --model_filename, --resum
 additions: --arch, --num_classes, --synthetic, --data_root, --image_size, --backend, --device,
 --bucket_mb, --workers, --eval_every, --steps_per_epoch, --precision, --graph, --data_on_device,
 --benchmark_steps, --label_smoothing, --mixup_alpha, --cutmix_alpha, --mix_prob, --mix_switch_prob,
---data_format, --rrc_scale, --rrc_ratio, --eval_crop, --norm.
+--data_format, --rrc_scale, --rrc_ratio, --eval_crop, --norm, --ema_decay, --ema_every, --ema_warmup.
 
 --data_format npy trains on a folder's images at any size: {data_root}/train_images.npy (uint8 [N, H, W, C]) and
 train_labels.npy (int64 [N]), val_* likewise (scripts/make_image_arrays.py writes them), live in device memory and
@@ -35,7 +35,7 @@ from ..data import (CIFAR10, CifarTransform, DeviceBatches, DeviceImageDataset, 
 from ..data.datasets import CIFAR_MEAN, CIFAR_STD, IMAGENET_MEAN, IMAGENET_STD
 from ..models import ARCHS
 from ..ops import CrossEntropyLoss, backward, top1_correct
-from ..optim import LARS, SGD
+from ..optim import LARS, SGD, WeightEMA
 from ..utils.checkpoint import load_checkpoint, resume_state, save_checkpoint, set_rng_state
 from ..utils.graphs import CapturedStep
 
@@ -80,7 +80,39 @@ def build_argparser(variant: str = "main") -> argparse.ArgumentParser:
     add_layerwise_args(p, "sgd", "lars")
     add_recipe_args(p)
     add_data_args(p)
+    add_ema_args(p)
     return p
+
+
+def add_ema_args(p):
+    """Weight EMA (optim.WeightEMA): averaged weights for evaluation and a second checkpoint."""
+    p.add_argument("--ema_decay", type=float, default=0.0,
+                   help="decay of the exponential moving average of the weights and BatchNorm statistics, in [0, 1) "
+                        "(0 = off): evaluated and checkpointed next to the trained weights")
+    p.add_argument("--ema_every", type=int, default=1, help="average on every K-th applied optimizer update")
+    p.add_argument("--ema_warmup", type=int, default=1, choices=[0, 1],
+                   help="1: decay min(--ema_decay, (1 + s) / (10 + s)) at the s-th averaging update")
+
+
+def check_ema_args(parser, args):
+    if not (math.isfinite(args.ema_decay) and 0 <= args.ema_decay < 1):
+        parser.error("--ema_decay must lie in [0, 1)")
+    if args.ema_every < 1:
+        parser.error("--ema_every must be at least 1")
+
+
+def ema_of(args, model, optimizer):
+    """The WeightEMA of the run, or None with --ema_decay 0 (then nothing of it is built)."""
+    if not getattr(args, "ema_decay", 0.0) > 0:
+        return None
+    return WeightEMA(model, decay=args.ema_decay, warmup=bool(args.ema_warmup), every=args.ema_every,
+                     optimizer=optimizer)
+
+
+def ema_path(path: str) -> str:
+    """<stem>.ema<ext>: the averaged weights next to the trained ones."""
+    stem, ext = os.path.splitext(path)
+    return stem + ".ema" + ext
 
 
 def add_data_args(p):
@@ -307,12 +339,17 @@ def run(args) -> dict:
         meta = load_checkpoint(ddp, model_filepath, map_location=device, optimizer=optimizer)
         start_epoch = int(meta.get("next_epoch", 0))
         set_rng_state(meta.get("rng"))
+    ema = ema_of(args, ddp, optimizer)   # (a copy of the weights as they are now: the loaded ones on --resume)
+    if ema is not None and args.resume and "ema" in meta:
+        ema.load_state_dict(meta["ema"])   # after the optimizer's: the step counter it last saw is the restored one
 
     def train_step(x, y, y_b=None, lam=None):
         optimizer.zero_grad()
         loss = criterion(ddp(x), y) if y_b is None else criterion(ddp(x), y, y_b, lam)
         backward(loss)
         optimizer.step()
+        if ema is not None:
+            ema.update()
         return loss
 
     captured = None
@@ -341,11 +378,20 @@ def run(args) -> dict:
     def eval_and_save(epoch, next_epoch):
         state = resume_state(next_epoch)   # RNG states of the epoch boundary, taken before evaluating
         accuracy = evaluate(model, device, test_loader)
+        if ema is not None:
+            state["ema"] = ema.state_dict()
         save_checkpoint(ddp, model_filepath, optimizer=optimizer, extra=state, rank=rank)
         print("-" * 75)
         print("Epoch: {}, Accuracy: {}".format(epoch, accuracy))
         print("-" * 75)
         history["accuracy"].append(accuracy)
+        if ema is not None:
+            with ema.applied():   # the model holds the averaged weights and BN statistics
+                ema_accuracy = evaluate(model, device, test_loader)
+                save_checkpoint(ddp, ema_path(model_filepath), rank=rank)   # reference layout, atomic, rank 0
+            print("Epoch: {}, EMA Accuracy: {}".format(epoch, ema_accuracy))
+            print("-" * 75)
+            history.setdefault("ema_accuracy", []).append(ema_accuracy)
 
     try:
         for epoch in range(start_epoch, args.num_epochs):
@@ -427,4 +473,5 @@ def main(variant="main", argv=None):
     check_layerwise_args(parser, args, "sgd")
     check_recipe_args(parser, args)
     check_data_args(parser, args)
+    check_ema_args(parser, args)
     return run(args)

@@ -44,7 +44,8 @@ from ..ops import (BCEDiceLoss, BCEWithLogitsLoss, CEDiceLoss, CrossEntropyLoss,
 from ..optim import LAMB, Adam, clip_grad_norm_
 from ..utils.graphs import CapturedStep
 from ..utils.checkpoint import load_checkpoint, resume_state, save_checkpoint, set_rng_state
-from .classification import add_layerwise_args, check_layerwise_args, schedule_of, use_graph
+from .classification import (add_ema_args, add_layerwise_args, check_ema_args, check_layerwise_args, ema_of, ema_path,
+                             schedule_of, use_graph)
 
 
 def build_argparser() -> argparse.ArgumentParser:
@@ -106,6 +107,7 @@ def build_argparser() -> argparse.ArgumentParser:
     add_layerwise_args(p, "adam", "lamb")
     p.add_argument("--weight_decay", type=float, default=None,
                    help="weight decay (default: 0 for adam, 0.01 for lamb)")
+    add_ema_args(p)
     return p
 
 
@@ -303,6 +305,11 @@ def run(args) -> dict:
         meta = load_checkpoint(ddp, model_filepath, map_location=device, optimizer=optimizer)
         start_epoch = int(meta.get("next_epoch", 0))
         set_rng_state(meta.get("rng"))
+    # averaged weights (--ema_decay): the optimizer's device step counter tells a skipped update (the clip hand-off's
+    # non-finite norm) from an applied one
+    ema = ema_of(args, ddp, optimizer)
+    if ema is not None and args.resume and "ema" in meta:
+        ema.load_state_dict(meta["ema"])   # after the optimizer's
     args.graph = use_graph(args, device, pixels=args.batch_size * args.image_size * args.image_size,
                            comm_backend=getattr(comm, "backend", "single"))
 
@@ -316,7 +323,21 @@ def run(args) -> dict:
         # collective NaN/Inf guard: a non-finite all-reduced grad norm skips the step on all ranks
         clip_grad_norm_(model.parameters(), max_norm=args.max_norm, optimizer=optimizer)
         optimizer.step()
+        if ema is not None:
+            ema.update()
         return loss
+
+    def save(state):
+        if ema is not None:
+            state["ema"] = ema.state_dict()
+        save_checkpoint(ddp, model_filepath, optimizer=optimizer, extra=state, rank=rank)
+
+    def ema_dice():
+        """Dice of the averaged model; its weights go next to the trained ones in the reference's layout."""
+        with ema.applied():
+            d = evaluate_model(model, device, test_loader, K, args.ignore_index)
+            save_checkpoint(ddp, ema_path(model_filepath), rank=rank)
+        return d
 
     S = args.image_size
     x_static = torch.zeros(args.batch_size, args.in_channels, S, S, device=device)
@@ -364,17 +385,23 @@ def run(args) -> dict:
             if (epoch + 1) % args.eval_every == 0 and rank == 0:
                 state = resume_state(epoch + 1)   # epoch-boundary RNG states, taken before evaluating
                 dice = evaluate_model(model, device, test_loader, K, args.ignore_index)
-                save_checkpoint(ddp, model_filepath, optimizer=optimizer, extra=state, rank=rank)
+                save(state)
                 print("-" * 75)
                 print(f"Epoch {epoch + 1} Dice Score: {dice:.4f}")
                 print("-" * 75)
                 log(f"Epoch {epoch + 1} | Dice Score: {dice:.4f}")
                 history["dice"].append(dice)
+                if ema is not None:
+                    d = ema_dice()
+                    print(f"Epoch {epoch + 1} EMA Dice Score: {d:.4f}")
+                    print("-" * 75)
+                    log(f"Epoch {epoch + 1} | EMA Dice Score: {d:.4f}")
+                    history.setdefault("ema_dice", []).append(d)
         if rank == 0:
             print("\n" + "=" * 80 + "\nTRAINING COMPLETED - FINAL EVALUATION\n" + "=" * 80)
             state = resume_state(args.num_epochs)
             final = evaluate_model(model, device, test_loader, K, args.ignore_index)
-            save_checkpoint(ddp, model_filepath, optimizer=optimizer, extra=state, rank=rank)
+            save(state)
             print(f"FINAL DICE COEFFICIENT: {final:.4f}\n" + "=" * 80 + "\n")
             log("=" * 80)
             log("FINAL TRAINING RESULTS")
@@ -385,6 +412,10 @@ def run(args) -> dict:
             log(f"Model saved to: {model_filepath}")
             log("=" * 80)
             history["final_dice"] = final
+            if ema is not None:
+                history["final_ema_dice"] = ema_dice()
+                print(f"FINAL EMA DICE COEFFICIENT: {history['final_ema_dice']:.4f}")
+                log(f"Final EMA Dice Coefficient: {history['final_ema_dice']:.4f}")
     finally:
         parallel.destroy_distributed()
     return history
@@ -396,6 +427,7 @@ def parse_args(argv=None):
     if args.num_classes < 1:
         p.error(f"--num_classes must be >= 1, got {args.num_classes}")
     check_layerwise_args(p, args, "adam")
+    check_ema_args(p, args)
     try:
         aug = seg_aug_config(args)
     except ValueError as e:

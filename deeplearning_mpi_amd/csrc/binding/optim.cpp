@@ -1,6 +1,6 @@
 // Torch binding of the optimisers on flat fp32 buffers (kernels/optim.hip) and the layer-wise family over the
-// segment / chunk tables of ParamArena.segments() (optim_layerwise.hip).  sgd_step, adam_step, grad_norm and scale_
-// take their buffers from the caller (NativeBackend) unchecked.
+// segment / chunk tables of ParamArena.segments() (optim_layerwise.hip), and the weight EMA (ema.hip).  sgd_step,
+// adam_step, grad_norm and scale_ take their buffers from the caller (NativeBackend) unchecked.
 #include <algorithm>
 
 #include "common.h"
@@ -125,6 +125,51 @@ void lamb_update(at::Tensor p, const at::Tensor& m, const at::Tensor& v, const a
                           t.T, ptr<float>(tab), (float)eps, (float)wd, cur_stream()),
         "lamb_update");
 }
+
+// ---- weight EMA (ema.hip): e toward w over the flat masters, eb toward b over the flat BN statistics ----
+bool overlaps(const at::Tensor& a, const at::Tensor& b) {
+  const char *a0 = ptr<char>(a), *b0 = ptr<char>(b);
+  return a0 < b0 + b.nbytes() && b0 < a0 + a.nbytes();
+}
+// the second range of both launches: both or neither, the same length, disjoint
+int64_t second_range(const c10::optional<at::Tensor>& a, const c10::optional<at::Tensor>& b, const char* fn,
+                     const char* an, const char* bn) {
+  if (given(a) != given(b)) fail(fn, std::string(an) + " and " + bn + " come together");
+  if (!given(a)) return 0;
+  dense(*a, at::kFloat, a->numel(), fn, an);
+  dense(*b, at::kFloat, a->numel(), fn, bn);
+  if (a->numel() && overlaps(*a, *b)) fail(fn, std::string(an) + " overlaps " + bn);
+  return a->numel();
+}
+void ema_update(at::Tensor e, const at::Tensor& w, const c10::optional<at::Tensor>& eb,
+                const c10::optional<at::Tensor>& b, at::Tensor state, const c10::optional<at::Tensor>& skip_flag,
+                const c10::optional<at::Tensor>& counter, int64_t every, bool warmup, double decay,
+                bool advance) {
+  const int64_t n = e.numel();
+  dense(e, at::kFloat, n, "ema_update", "e");
+  dense(w, at::kFloat, n, "ema_update", "w");
+  if (n && overlaps(e, w)) fail("ema_update", "e overlaps w");
+  const int64_t nb = second_range(eb, b, "ema_update", "eb", "b");
+  shaped(state, at::kFloat, {8}, "ema_update", "state");
+  if (state.device() != e.device()) fail("ema_update", "state must be on the device of e");
+  dense(skip_flag, at::kFloat, 1, "ema_update", "skip_flag");
+  dense(counter, at::kFloat, 1, "ema_update", "counter");
+  if (every < 1 || every > (1 << 24)) fail("ema_update", "every must be in [1, 2^24]");
+  if (!(decay >= 0.0 && decay < 1.0)) fail("ema_update", "decay must be in [0, 1)");
+  check(dlmpi_ema_update(ptr<float>(e), ptr<float>(w), n, optr<float>(eb), optr<float>(b), nb, ptr<float>(state),
+                         optr<float>(skip_flag), optr<float>(counter), (int)every, warmup ? 1 : 0, decay,
+                         advance ? 1 : 0, cur_stream()),
+        "ema_update");
+}
+void ema_swap(at::Tensor a, at::Tensor b, const c10::optional<at::Tensor>& a2, const c10::optional<at::Tensor>& b2) {
+  const int64_t n = a.numel();
+  dense(a, at::kFloat, n, "ema_swap", "a");
+  dense(b, at::kFloat, n, "ema_swap", "b");
+  if (n && overlaps(a, b)) fail("ema_swap", "a overlaps b");
+  const int64_t n2 = second_range(a2, b2, "ema_swap", "a2", "b2");
+  check(dlmpi_swap_f32(ptr<float>(a), ptr<float>(b), n, optr<float>(a2), optr<float>(b2), n2, cur_stream()),
+        "ema_swap");
+}
 }  // namespace
 
 void register_optim(pybind11::module& m) {
@@ -137,6 +182,8 @@ void register_optim(pybind11::module& m) {
   m.def("lars_update", &lars_update);
   m.def("lamb_moments", &lamb_moments);
   m.def("lamb_update", &lamb_update);
+  m.def("ema_update", &ema_update);
+  m.def("ema_swap", &ema_swap);
   m.def("lw_chunk", []() { return dlmpi_lw_chunk(); });
   m.def("lw_tab", []() { return dlmpi_lw_tab(); });
 }

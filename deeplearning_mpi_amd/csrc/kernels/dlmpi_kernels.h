@@ -477,6 +477,16 @@ hipError_t dlmpi_clip_coef(const float* partial, int nblk, float max_norm, float
                            hipStream_t s);
 hipError_t dlmpi_scale_f32(float* x, int64_t n, const float* coef, hipStream_t s);
 
+// weight EMA (ema.hip).  One launch lerps e toward w (n) and eb toward b (nb, may be 0) by 1 - d_t, then one thread
+// advances state (fp32 [8] = {n, s, counter seen, omd, fired, spare x 3}).  skip_flag (non-zero = skipped) and
+// counter (the optimizer's device step count: unmoved = skipped) are optional; d_t = warmup ? min(decay,
+// (1 + s) / (10 + s)) : decay in fp64; an update fires on every `every`-th applied optimizer update.
+hipError_t dlmpi_ema_update(float* e, const float* w, int64_t n, float* eb, const float* b, int64_t nb, float* state,
+                            const float* skip_flag, const float* counter, int every, int warmup, double decay,
+                            int advance, hipStream_t s);   // advance 0: the update alone, the state untouched
+// a <-> b (n) and a2 <-> b2 (n2, may be 0) in one launch
+hipError_t dlmpi_swap_f32(float* a, float* b, int64_t n, float* a2, float* b2, int64_t n2, hipStream_t s);
+
 // layer-wise optimizers (optim_layerwise.hip).  chunks: int32 [nchunks][4] = {segment, length, start lo,
 // start hi}, length <= dlmpi_lw_chunk(), start relative to the buffers (n elements each); partial: fp32
 // [2][nchunks]; chunk_first: int32 [T + 1]; flags: int32 [T] (bit 0 no decay, bit 1 no adaptation);

@@ -606,6 +606,16 @@ class NativeBackend:
                           1, 0.0, wd, eps, b1, b2, kind, lr, warm, total, min_lr, power)
         self.C.lamb_update(p, m, v, s.chunks, plan.flags, s.extent, plan.tab, eps, wd)
 
+    # weight EMA (csrc/kernels/ema.hip): e toward w (and eb toward b, the flat BN statistics) in one launch;
+    # state: fp32 [8], the device-side counters and the decision's memory (optim.WeightEMA)
+    def ema_update(self, e, w, eb, b, state, skip_flag, counter, every, warmup, decay, advance=True):
+        """advance False: the update alone, the state untouched (all but the last of a per-tensor series)."""
+        self.C.ema_update(e, w, eb, b, state, skip_flag, counter, int(every), bool(warmup), float(decay),
+                          bool(advance))
+
+    def ema_swap(self, a, b, a2=None, b2=None):
+        self.C.ema_swap(a, b, a2, b2)
+
     # ---------------- utilities (per-step glue on our own kernels) ----------------
     def fill_(self, t, v):
         self.C.fill_(t, float(v))
@@ -1205,6 +1215,44 @@ class RefBackend:
         tab[0], tab[1], tab[2], tab[3], tab[5] = lr_t, bc1, bc2, 0.0, float(done == 0)
         tab[6], tab[7] = 1 - b1 ** (done + 2), 1 - b2 ** (done + 2)   # the next update's
         step.add_(1)
+
+    # weight EMA: the decision of ema.hip's ema_decide on host copies of the same state vector, the update in
+    # the buffers' dtype (fp64 arenas average in fp64; state[3] then holds omd rounded to fp32)
+    def ema_update(self, e, w, eb, b, state, skip_flag, counter, every, warmup, decay, advance=True):
+        if not 0.0 <= decay < 1.0 or every < 1:
+            raise RuntimeError("ema_update: decay must be in [0, 1) and every >= 1")
+        if e.numel() != w.numel() or (eb is None) != (b is None) or (eb is not None and eb.numel() != b.numel()):
+            raise RuntimeError("ema_update: mismatched lengths")
+        st = state.tolist()
+        cnt = float(counter.reshape(-1)[0]) if counter is not None else None
+        applied = not (skip_flag is not None and float(skip_flag.reshape(-1)[0]) != 0) and \
+            not (cnt is not None and cnt == st[2])
+        fire = applied and (st[0] + 1) % every == 0
+        omd = 1.0 - (min(decay, (1 + st[1]) / (10 + st[1])) if warmup else decay)
+        if fire:
+            omd = torch.tensor(omd, dtype=e.dtype).item()
+            # the product rounded on its own: add_(alpha=) fuses it in torch's vector loop and not in its tail, so
+            # the result would depend on how the elements are split over launches
+            e.add_((w - e).mul_(omd))
+            if eb is not None and eb.numel():
+                eb.add_((b - eb).mul_(omd))
+        if not advance:
+            return
+        if fire:
+            state[1] += 1
+            state[3] = omd
+        if applied:
+            state[0] += 1
+        if cnt is not None:
+            state[2] = cnt
+        state[4] = float(fire)
+
+    def ema_swap(self, a, b, a2=None, b2=None):
+        for x, y in ((a, b), (a2, b2)):
+            if x is not None:
+                t = x.clone()
+                x.copy_(y)
+                y.copy_(t)
 
     def fill_(self, t, v):
         t.fill_(v)

@@ -9,6 +9,9 @@ single arena the optimizers fall back to one kernel per parameter tensor.
 ``LARS`` and ``LAMB`` add layer-wise trust ratios for a large global batch: two chunk-indexed passes
 over the flat buffers plus one finishing block (csrc/kernels/optim_layerwise.hip), with the step
 count, the learning-rate schedule and the skip decision on the device.
+
+``WeightEMA`` (optim/ema.py) averages the master weights and the BatchNorm statistics after each
+applied update: one launch over the arena's two flat buffers, its counters on the device as well.
 """
 from __future__ import annotations
 
@@ -384,3 +387,6 @@ def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0, optimiz
     if optimizer is not None and hasattr(optimizer, "clip"):
         optimizer.clip = coef[2:4]   # grads already scaled in place: scale 1, keep the skip flag
     return norm[0]
+
+
+from .ema import WeightEMA  # noqa: E402  (after the optimizers it refers to)
