@@ -1,5 +1,5 @@
 """What assembling an augmented segmentation batch costs on the GPU.  Run by hand; the results are kept in
-profiles/seg_aug/README.md.
+profiles/seg_aug/README.md and profiles/seg_elastic/README.md.
 
 Batch assembly at 16 x 3 x 512 x 512 from a device-resident set of 64 pairs, float32 masks (the binary trainer)
 and int64 masks (class indices), in these variants:
@@ -9,6 +9,12 @@ and int64 masks (class indices), in these variants:
   identity     the seg_aug kernel with identity rows (the same pixels as the gathers)
   rot_scale    the seg_aug kernel with a drawn table: flips, scale in [0.8, 1.25], +-30 degrees, +-5 % translation
   *_1col       the last two into outputs one element off the 16-byte grid: the kernel's one-column-per-thread path
+  *_el3, *_el16   the elastic kernel (seg_elastic.hip) on the same two affine tables, control points of 10 px
+               deviation on G = 3 and G = 16 cells per axis; over_affine: its time over the affine kernel's on the
+               same table in the same round
+  identity_el16_wide   the G = 16 launch with the row table's cells set to 0 and G - 1 in turn, so that every block's
+               window is all 19 lattice rows and not the 4 a 32-row tile of 512 touches: the same LDS, occupancy,
+               taps and stores, 15 more rows in the column pass (stage 2), whose cost is 4 / 15 of the difference
 
 Each reports GB/s over a byte model: the output written once, the source read once per tap footprint (the distinct
 source pixels a sample's taps touch: all of them for the gathers and the identity, counted from the table for the
@@ -17,6 +23,7 @@ alternated, --repeats rounds (min / median / max).
 Usage: python benchmarks/seg_aug_bench.py [--launches N] [--repeats N] [--out FILE]
 """
 import argparse
+import dataclasses
 import json
 import os
 import statistics
@@ -27,7 +34,8 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from deeplearning_mpi_amd.data import DeviceCachedDataset, DeviceSegDataset, SegAugConfig  # noqa: E402
+from deeplearning_mpi_amd.data import (DeviceCachedDataset, DeviceSegDataset, SegAugConfig,  # noqa: E402
+                                       seg_elastic_field)  # noqa: E402
 
 DEV = "cuda"
 N, B, C, S = 64, 16, 3, 512
@@ -75,14 +83,17 @@ def alternate(variants, launches, repeats):
             for k, v in t.items()}
 
 
-def footprint(table, idx, H, W, Ho, Wo):
-    """(image pixels, mask pixels) of the source that the batch's taps touch, summed over its samples."""
+def footprint(table, idx, H, W, Ho, Wo, field=None):
+    """(image pixels, mask pixels) of the source that the batch's taps touch, summed over its samples; `field`:
+    the elastic displacement of each sample of the batch, int64 [B, 2, Ho, Wo]."""
     t = torch.as_tensor(table).to(torch.int64)[idx.cpu()]
     xs = torch.arange(Wo, dtype=torch.int64).view(1, Wo)
     ys = torch.arange(Ho, dtype=torch.int64).view(Ho, 1)
     img = msk = 0
-    for a, b, c, d, e, f in t.tolist():
+    for i, (a, b, c, d, e, f) in enumerate(t.tolist()):
         X, Y = a * xs + b * ys + c, d * xs + e * ys + f
+        if field is not None:
+            X, Y = X + field[i, 0], Y + field[i, 1]
 
         def count(ix, iy):
             ok = (ix >= 0) & (ix < W) & (iy >= 0) & (iy < H)
@@ -109,24 +120,45 @@ def bench(num_classes, launches, repeats):
     yb = torch.empty(B * S * S + 2, dtype=src.masks.dtype, device=DEV)
     off = (xb[1:1 + B * C * S * S].view(B, C, S, S), yb[1:1 + B * S * S].view(B, S, S))
     ident.table(0), drawn.table(0)   # drawn and copied once per epoch: not part of a step
-    res = alternate({"gathers": lambda: cached.batch(idx),
-                     "gathers_out": lambda: cached.batch(idx, out=out),
-                     "identity": lambda: ident.batch(idx, 0, out=out),
-                     "rot_scale": lambda: drawn.batch(idx, 0, out=out),
-                     "identity_1col": lambda: ident.batch(idx, 0, out=off),
-                     "rot_scale_1col": lambda: drawn.batch(idx, 0, out=off)}, launches, repeats)
+    variants = {"gathers": lambda: cached.batch(idx),
+                "gathers_out": lambda: cached.batch(idx, out=out),
+                "identity": lambda: ident.batch(idx, 0, out=out),
+                "rot_scale": lambda: drawn.batch(idx, 0, out=out),
+                "identity_1col": lambda: ident.batch(idx, 0, out=off),
+                "rot_scale_1col": lambda: drawn.batch(idx, 0, out=off)}
+    elastic = {}                     # the same affine tables (the elastic draw has streams of its own)
+    for name, cfg in (("identity", SegAugConfig()), ("rot_scale", DRAWN)):
+        for G in (3, 16):
+            ds = DeviceSegDataset(src, DEV, dataclasses.replace(cfg, elastic_sigma=10.0, elastic_grid=G), seed=1,
+                                  mask_fill=fill)
+            assert torch.equal(ds.table(0), (ident if name == "identity" else drawn).table(0))
+            elastic[f"{name}_el{G}"] = ds
+            variants[f"{name}_el{G}"] = lambda ds=ds: ds.batch(idx, 0, out=out)
+    wide = DeviceSegDataset(src, DEV, SegAugConfig(elastic_sigma=10.0, elastic_grid=16), seed=1, mask_fill=fill)
+    wide.table(0)
+    wide._ey[0::2, 0], wide._ey[1::2, 0] = 0, 15
+    variants["identity_el16_wide"] = lambda: wide.batch(idx, 0, out=out)
+    res = alternate(variants, launches, repeats)
     px = B * S * S
     written = px * (C * 4 + mb)
     fi, fm = footprint(drawn.table(0).cpu(), idx, S, S, S, S)
     model = {"gathers": 2 * written, "gathers_out": 4 * written, "identity": 2 * written,
              "rot_scale": written + fi * C * 4 + fm * mb}
     model.update(identity_1col=model["identity"], rot_scale_1col=model["rot_scale"])
+    for k, ds in {**elastic, "identity_el16_wide": wide}.items():
+        field = seg_elastic_field(ds.lattice(0).cpu()[idx.cpu()], ds._ex.cpu(), ds._ey.cpu())
+        ei, em = footprint(ds.table(0).cpu(), idx, S, S, S, S, field)
+        model[k] = written + ei * C * 4 + em * mb
     base = res["gathers"]["median_us"]
     for k, v in res.items():
         v["byte_model_bytes"] = model[k]
         v["GBps_at_median"] = round(model[k] / v["median_us"] / 1e3, 1)
         v["over_gathers"] = round(v["median_us"] / base, 3)
         v["share_of_unet512_step"] = round(v["median_us"] / 1e3 / STEP_MS, 4)
+        if "_el" in k:
+            v["over_affine"] = round(v["median_us"] / res[k.split("_el")[0]]["median_us"], 3)
+    res["identity_el16"]["stage2_us"] = round(
+        (res["identity_el16_wide"]["median_us"] - res["identity_el16"]["median_us"]) * 4 / 15, 2)
     return {"mask_dtype": str(src.masks.dtype), "shape": [B, C, S, S],
             "rot_scale_footprint_share": round(fi / px, 4), **res}
 

@@ -19,7 +19,10 @@ sigmoid form for --num_classes 1, softmax form for K > 1 (ops.bce_dice_loss / ce
 sums and gradient ride in the cross-entropy kernels' passes: one forward, one finish, one backward.
 --aug_hflip / --aug_vflip / --aug_scale / --aug_rotate / --aug_translate / --aug_prob (defaults: none) augment
 the training split on the device: the pairs stay resident and one kernel per batch gathers and resamples image
-and mask (data/seg_aug.py, DeviceSegDataset); evaluation is unchanged.
+and mask (data/seg_aug.py, DeviceSegDataset); evaluation is unchanged.  --aug_elastic_sigma PX (default 0: none)
+adds the U-Net paper's elastic deformation in that same launch: a cubic B-spline displacement field over
+--aug_elastic_grid cells per axis whose control points are normal with PX source pixels of deviation, for a share
+--aug_elastic_prob of the samples (csrc/kernels/seg_elastic.hip).
 """
 from __future__ import annotations
 
@@ -104,6 +107,10 @@ def build_argparser() -> argparse.ArgumentParser:
                    help="translation uniform in +-F of the image width / height")
     p.add_argument("--aug_prob", type=float, default=1.0,
                    help="probability that a sample gets its scale / rotation / translation (flips are drawn apart)")
+    p.add_argument("--aug_elastic_sigma", type=float, default=0.0, metavar="PX",
+                   help="elastic deformation: deviation of the B-spline control points in source pixels (0: none)")
+    p.add_argument("--aug_elastic_grid", type=int, default=3, metavar="G", help="cells per axis of the elastic lattice")
+    p.add_argument("--aug_elastic_prob", type=float, default=1.0, help="probability that a sample is deformed")
     add_layerwise_args(p, "adam", "lamb")
     p.add_argument("--weight_decay", type=float, default=None,
                    help="weight decay (default: 0 for adam, 0.01 for lamb)")
@@ -160,7 +167,10 @@ def seg_aug_config(args) -> SegAugConfig:
     """The --aug_* flags (absent on namespaces that callers build themselves: the defaults, no augmentation)."""
     return SegAugConfig(hflip=getattr(args, "aug_hflip", 0.0), vflip=getattr(args, "aug_vflip", 0.0),
                         scale=tuple(getattr(args, "aug_scale", (1.0, 1.0))), rotate=getattr(args, "aug_rotate", 0.0),
-                        translate=getattr(args, "aug_translate", 0.0), prob=getattr(args, "aug_prob", 1.0))
+                        translate=getattr(args, "aug_translate", 0.0), prob=getattr(args, "aug_prob", 1.0),
+                        elastic_sigma=getattr(args, "aug_elastic_sigma", 0.0),
+                        elastic_grid=getattr(args, "aug_elastic_grid", 3),
+                        elastic_prob=getattr(args, "aug_elastic_prob", 1.0))
 
 
 def build_data_loaders(args, device):

@@ -32,6 +32,9 @@ EXT_SUFFIX = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
 C_SO = os.path.join(HERE, "_C" + EXT_SUFFIX)
 MPI_SO = os.path.join(HERE, "_mpi" + EXT_SUFFIX)
 
+# hipcc flags of single kernel files: scalar fp32 only (no packed v_pk_*_f32) where every lerp is rounded on its own
+FILE_FLAGS = {"seg_elastic.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
 
 def _headers():
     return glob.glob(os.path.join(CSRC, "**", "*.h"), recursive=True)
@@ -106,6 +109,7 @@ def build_kernels(jobs=8, force=False, verbose=False):
     def one(so):
         s, o = so
         extra = os.environ.get("DLMPI_HIPCC_FLAGS", "").split()   # experiments: extra hipcc flags
+        extra += FILE_FLAGS.get(os.path.basename(s), [])
         _run([hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", *extra,
               "-c", s, "-o", o], verbose)
         return o

@@ -1,6 +1,6 @@
-// Torch binding of the device-resident input pipeline (kernels/data.hip, seg_aug.hip, rrc.hip).  Nothing here
-// synchronises, with one exception outside the step: image_rrc_batch reads a crop table back the first time it
-// sees it.
+// Torch binding of the device-resident input pipeline (kernels/data.hip, seg_aug.hip, seg_elastic.hip, rrc.hip).
+// Nothing here synchronises, with one exception outside the step: image_rrc_batch reads a crop table back the
+// first time it sees it.
 #include <cmath>
 #include <vector>
 
@@ -71,9 +71,14 @@ void mix_batch_(at::Tensor x, const at::Tensor& labels, int kind, double lam, in
 // Segmentation augmentation (seg_aug.hip): images fp32 [N, C, H, W] and masks [N, H, W] (float32 | int64) gathered
 // by idx [B] and resampled through rows idx[b] of table (int32 [N, 6], Q16) into out [B, C, Ho, Wo] and out_mask
 // [B, Ho, Wo].  idx values are trusted.
-void seg_aug_batch(const at::Tensor& images, const at::Tensor& masks, const at::Tensor& idx, const at::Tensor& table,
-                   double image_fill, double mask_fill, at::Tensor out, at::Tensor out_mask) {
-  const char* fn = "seg_aug_batch";
+struct SegOperands {
+  int B, C, H, W, Ho, Wo;
+  int64_t N;
+  bool i64;
+};
+SegOperands seg_operands(const char* fn, const at::Tensor& images, const at::Tensor& masks, const at::Tensor& idx,
+                         const at::Tensor& table, double image_fill, double mask_fill, const at::Tensor& out,
+                         const at::Tensor& out_mask) {
   if (layout_fault(images, at::kFloat) != Fault::none || images.dim() != 4 || images.numel() < 1)
     fail(fn, "images must be a contiguous fp32 [N, C, H, W] GPU tensor");
   const int64_t N = images.size(0), C = images.size(1), H = images.size(2), W = images.size(3);
@@ -91,10 +96,35 @@ void seg_aug_batch(const at::Tensor& images, const at::Tensor& masks, const at::
   if (H * W > INT32_MAX || out_mask.numel() > INT32_MAX || C > INT32_MAX)
     fail(fn, "an images plane and out_mask hold at most 2^31 - 1 pixels");
   if (!std::isfinite(image_fill) || !std::isfinite(mask_fill)) fail(fn, "image_fill and mask_fill must be finite");
-  check(dlmpi_seg_aug_batch(ptr<float>(images), masks.data_ptr(), i64 ? 1 : 0, ptr<int64_t>(idx), ptr<int>(table),
-                            (int)B, (int)C, (int)H, (int)W, (int)Ho, (int)Wo, (float)image_fill, (float)mask_fill,
+  return {(int)B, (int)C, (int)H, (int)W, (int)Ho, (int)Wo, N, i64};
+}
+void seg_aug_batch(const at::Tensor& images, const at::Tensor& masks, const at::Tensor& idx, const at::Tensor& table,
+                   double image_fill, double mask_fill, at::Tensor out, at::Tensor out_mask) {
+  const SegOperands o = seg_operands("seg_aug_batch", images, masks, idx, table, image_fill, mask_fill, out, out_mask);
+  check(dlmpi_seg_aug_batch(ptr<float>(images), masks.data_ptr(), o.i64 ? 1 : 0, ptr<int64_t>(idx), ptr<int>(table),
+                            o.B, o.C, o.H, o.W, o.Ho, o.Wo, (float)image_fill, (float)mask_fill,
                             (int64_t)std::llround(mask_fill), ptr<float>(out), out_mask.data_ptr(), cur_stream()),
         "seg_aug_batch");
+}
+// The same with an elastic deformation (seg_elastic.hip): lattice int32 [N, 2, G + 3, G + 3] (Q16 control points of
+// a cubic B-spline, G cells per axis), ex int32 [Wo, 5] and ey int32 [Ho, 5] (cell and four Q20 weights per output
+// column / row).  The tables' contents are not read here (that would synchronise): the kernel clamps every cell.
+void seg_elastic_batch(const at::Tensor& images, const at::Tensor& masks, const at::Tensor& idx,
+                       const at::Tensor& table, const at::Tensor& lattice, int64_t G, const at::Tensor& ex,
+                       const at::Tensor& ey, double image_fill, double mask_fill, at::Tensor out,
+                       at::Tensor out_mask) {
+  const char* fn = "seg_elastic_batch";
+  const SegOperands o = seg_operands(fn, images, masks, idx, table, image_fill, mask_fill, out, out_mask);
+  if (G < 1 || G > 32) fail(fn, "G must lie in [1, 32], got " + std::to_string(G));
+  shaped(lattice, at::kInt, {o.N, 2, G + 3, G + 3}, fn, "lattice");
+  shaped(ex, at::kInt, {o.Wo, 5}, fn, "ex");
+  shaped(ey, at::kInt, {o.Ho, 5}, fn, "ey");
+  if (o.B > 65535 || o.Ho > 65535 * 32) fail(fn, "at most 65535 samples and 65535 * 32 output rows");
+  check(dlmpi_seg_elastic_batch(ptr<float>(images), masks.data_ptr(), o.i64 ? 1 : 0, ptr<int64_t>(idx),
+                                ptr<int>(table), ptr<int>(lattice), (int)G, ptr<int>(ex), ptr<int>(ey), o.B, o.C, o.H,
+                                o.W, o.Ho, o.Wo, (float)image_fill, (float)mask_fill,
+                                (int64_t)std::llround(mask_fill), ptr<float>(out), out_mask.data_ptr(), cur_stream()),
+        fn);
 }
 
 // RandomResizedCrop batch (rrc.hip): data uint8 [N, H, W, C] gathered by idx [B], cropped to rows idx[b] of table
@@ -179,6 +209,7 @@ void register_data(pybind11::module& m) {
   m.def("image_batch_mix", &image_batch_mix);
   m.def("mix_batch_", &mix_batch_);
   m.def("seg_aug_batch", &seg_aug_batch);
+  m.def("seg_elastic_batch", &seg_elastic_batch);
   m.def("image_rrc_batch", &image_rrc_batch);
   m.def("rrc_max_scale", []() { return dlmpi_rrc_max_scale(); });
 }

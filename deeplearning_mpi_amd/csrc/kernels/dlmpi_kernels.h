@@ -533,6 +533,14 @@ hipError_t dlmpi_mix_batch(float* x, const int64_t* labels, int B, int C, int H,
 hipError_t dlmpi_seg_aug_batch(const float* images, const void* masks, int mask_i64, const int64_t* idx,
                                const int* table, int B, int C, int H, int W, int Ho, int Wo, float image_fill,
                                float mask_fill_f, int64_t mask_fill_i, float* out, void* out_mask, hipStream_t s);
+// the same with an elastic deformation (seg_elastic.hip): the source coordinate of output pixel (x, y) gains the
+// displacement of a uniform cubic B-spline over sample idx[b]'s control lattice, `lattice` int32 [N][2][G + 3][G + 3]
+// in Q16 source pixels (x component, then y), G cells per axis, 1 <= G <= 32.  ex [Wo][5], ey [Ho][5]: per output
+// column / row the cell index and the four Q20 basis weights; cell indices are clamped into [0, G - 1] on the device.
+hipError_t dlmpi_seg_elastic_batch(const float* images, const void* masks, int mask_i64, const int64_t* idx,
+                                   const int* table, const int* lattice, int G, const int* ex, const int* ey, int B,
+                                   int C, int H, int W, int Ho, int Wo, float image_fill, float mask_fill_f,
+                                   int64_t mask_fill_i, float* out, void* out_mask, hipStream_t s);
 // RandomResizedCrop batch (rrc.hip): out[b] = normalize(flip(resize(crop(data[idx[b]])))) through row idx[b] of
 // `table` (int32 [N][5]: top, left, h, w, flip), anti-aliased bilinear; data [N][H][W][C] uint8 with C = 1 or 3,
 // out [B][C][Ho][Wo] fp32, out_labels[b] = labels[idx[b]].  The caller has checked that every box lies inside the

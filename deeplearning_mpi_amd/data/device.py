@@ -22,7 +22,8 @@ device-side gather:
   ``index_select`` gathers.
 * :class:`DeviceSegDataset` -- the same image / mask pairs with geometric augmentation (flip, scale, rotate,
   translate, crop; ``data/seg_aug.py``): a batch is ONE HIP kernel (``csrc/kernels/seg_aug.hip``) that gathers
-  and resamples image and mask through the sample's row of the epoch's parameter table.
+  and resamples image and mask through the sample's row of the epoch's parameter table; with an elastic
+  deformation, the kernel of ``csrc/kernels/seg_elastic.hip`` in its place.
 * :class:`DeviceBatches` -- iterates any of them in :class:`DistributedSampler` order (the epoch's index
   list goes to the device in one copy), optionally writing into fixed tensors so a captured
   hipGraph step can consume them without a copy.
@@ -38,7 +39,7 @@ import torch
 from .datasets import CIFAR10, CIFAR_MEAN, CIFAR_STD
 from .mix import KINDS, MixConfig, draw_mix, mix_reference
 from .rrc import RrcConfig, center_box, draw_rrc, rrc_reference
-from .seg_aug import SegAugConfig, draw_seg_aug, seg_aug_reference
+from .seg_aug import SegAugConfig, draw_seg_aug, draw_seg_elastic, seg_aug_reference, seg_elastic_axis
 
 _M32 = 0xFFFFFFFF
 
@@ -272,8 +273,10 @@ class DeviceSegDataset:
     nearest for the mask (``data/seg_aug.py``), into ``out_size = (Ho, Wo)`` (default: the source size).  The
     epoch's parameter table is drawn on the host and copied to the device when the epoch changes -- one small
     copy per epoch, none per step.  Mask pixels from outside the source are ``mask_fill`` (default 0.0 for float
-    masks; int64 masks must name theirs, usually the loss's ignore_index).  On a CPU device ``batch`` runs
-    :func:`seg_aug_reference`."""
+    masks; int64 masks must name theirs, usually the loss's ignore_index).  With ``aug.elastic_sigma > 0`` the
+    batch kernel is the elastic one (``csrc/kernels/seg_elastic.hip``) -- still one launch: the two axis tables are
+    built here, once, and the epoch's control lattices travel with its parameter table.  On a CPU device ``batch``
+    runs :func:`seg_aug_reference`."""
 
     def __init__(self, dataset, device, aug: SegAugConfig, seed=0, out_size=None, mask_fill=None):
         self.device = torch.device(device)
@@ -307,6 +310,11 @@ class DeviceSegDataset:
         self.aug, self.seed = aug, seed
         self.redraws = 0                 # tables drawn (and copied to the device) so far
         self._epoch = self._table = self._table_np = None
+        self.elastic = aug.elastic_sigma > 0
+        self._lattice = self._lattice_np = None
+        if self.elastic:                 # the axis tables depend on (G, Ho, Wo) alone
+            self._ex = torch.from_numpy(seg_elastic_axis(self.Wo, aug.elastic_grid)).to(self.device)
+            self._ey = torch.from_numpy(seg_elastic_axis(self.Ho, aug.elastic_grid)).to(self.device)
         self._native = None
         if self.device.type == "cuda":
             from .._ext import native
@@ -317,13 +325,24 @@ class DeviceSegDataset:
         return self.N
 
     def table(self, epoch: int) -> torch.Tensor:
-        """The parameter table of ``epoch`` on the device, int32 [N, 6]; redrawn when the epoch changes."""
+        """The parameter table of ``epoch`` on the device, int32 [N, 6]; redrawn when the epoch changes, and with
+        it the control lattices of an elastic dataset."""
         if self._epoch != int(epoch):
             self._table_np = draw_seg_aug(self.aug, self.seed, int(epoch), self.N, self.H, self.W, self.Ho, self.Wo)
             self._table = torch.from_numpy(self._table_np).to(self.device)
+            if self.elastic:
+                self._lattice_np = draw_seg_elastic(self.aug, self.seed, int(epoch), self.N)
+                self._lattice = torch.from_numpy(self._lattice_np).to(self.device)
             self._epoch = int(epoch)
             self.redraws += 1
         return self._table
+
+    def lattice(self, epoch: int) -> torch.Tensor:
+        """The control lattices of ``epoch`` on the device, int32 [N, 2, G + 3, G + 3]: drawn with :meth:`table`."""
+        if not self.elastic:
+            raise ValueError("this dataset has no elastic deformation (elastic_sigma is 0)")
+        self.table(epoch)
+        return self._lattice
 
     def batch(self, idx: torch.Tensor, epoch: int = 0, out=None):
         """idx: int64 dataset indices on the device -> {'image': fp32 [B, C, Ho, Wo], 'mask': [B, Ho, Wo]},
@@ -338,11 +357,15 @@ class DeviceSegDataset:
                 raise ValueError(f"out must be ([{B}, {self.C}, {self.Ho}, {self.Wo}], [{B}, {self.Ho}, {self.Wo}]), "
                                  f"got {tuple(x.shape)} and {tuple(y.shape)}")
         table = self.table(epoch)
-        if self._native is not None:
+        if self._native is not None and self.elastic:
+            self._native.seg_elastic_batch(self.images, self.masks, idx, table, self._lattice, self.aug.elastic_grid,
+                                           self._ex, self._ey, self.aug.image_fill, self.mask_fill, x, y)
+        elif self._native is not None:
             self._native.seg_aug_batch(self.images, self.masks, idx, table, self.aug.image_fill, self.mask_fill, x, y)
         else:
             xr, yr = seg_aug_reference(self.images, self.masks, idx, self._table_np, self.Ho, self.Wo,
-                                       self.aug.image_fill, self.mask_fill)
+                                       self.aug.image_fill, self.mask_fill, lattice=self._lattice_np,
+                                       grid=self.aug.elastic_grid if self.elastic else None)
             x.copy_(xr)
             y.copy_(yr)
         return {"image": x, "mask": y}

@@ -26,6 +26,21 @@ The parameters of an epoch are ONE table, int32 ``[N, 6]``, row ``i`` for datase
 from ``np.random.default_rng([seed, epoch])`` (:func:`draw_seg_aug`): a sample's augmentation is a function of
 ``(seed, epoch, index)`` alone -- not of the batch size, the rank count or its place in the batch -- and a resumed
 run repeats it.  The table goes to the device once per epoch; no device RNG is involved.
+
+Elastic deformation (``elastic_sigma > 0``; Ronneberger et al. 2015, section 3.1) adds a smooth displacement of the
+OUTPUT pixel to the affine source coordinate, ``X = a x + b y + c + dX(x, y)``, ``Y`` likewise with ``dY``.  The
+field is a uniform cubic B-spline over a per-sample control lattice ``D``, int32 ``[2, L, L]`` in Q16 source pixels
+(x component, then y), ``L = G + 3`` for ``G`` cells per axis.  Each output axis of ``n`` pixels has a table int32
+``[n, 5]`` (:func:`seg_elastic_axis`), rows ``(i, w0, w1, w2, w3)``: the cell of pixel centre ``p + 0.5`` and the
+four basis values in Q20, non-negative and summing to ``2^20`` exactly.  Columns first, then rows, rounded after
+each pass (:func:`seg_elastic_field`, and the same integers in ``csrc/kernels/seg_elastic.hip``)::
+
+    E_c[r][x] = (sum_a wx[x][a] D_c[r][ix[x] + a] + 2^19) >> 20
+    d_c(x, y) = (sum_b wy[y][b] E_c[iy[y] + b][x] + 2^19) >> 20
+
+so ``|d| <= max |D|``, a constant lattice is a pure translation and a zero lattice changes nothing, bit for bit.
+The lattices of an epoch are drawn by :func:`draw_seg_elastic` from streams of their own: the affine table does
+not move.
 """
 from __future__ import annotations
 
@@ -38,13 +53,21 @@ import torch
 
 Q = 65536          # Q16: one source pixel
 IDENTITY = (Q, 0, 0, 0, Q, 0)
+QW = 1 << 20       # Q20: the sum of the four basis weights of an elastic axis table
+MAX_GRID = 32      # cells per axis of an elastic lattice (the kernel's LDS holds G + 3 rows of the column pass)
+MAX_SIGMA = 1024   # so that |D| <= 4 sigma Q = 2^28 fits an int32 with room for the affine part
 
 
 @dataclass(frozen=True)
 class SegAugConfig:
     """``hflip`` / ``vflip``: probabilities of a flip; ``scale``: log-uniform in ``[lo, hi]``; ``rotate``: the angle
     uniform in +-``rotate`` degrees; ``translate``: tx, ty uniform in +-``translate`` * W and * H; with probability
-    ``1 - prob`` a sample keeps only its flips; ``image_fill``: the image value outside the source."""
+    ``1 - prob`` a sample keeps only its flips; ``image_fill``: the image value outside the source.
+
+    ``elastic_sigma``: standard deviation, in source pixels, of the CONTROL POINTS of the elastic displacement (10 in
+    the U-Net paper), 0: none.  The field itself is a B-spline blend of 16 of them, so it is smoother and smaller:
+    about 0.48 sigma per component in the interior.  ``elastic_grid``: cells per axis (3: the paper's coarse grid);
+    ``elastic_prob``: the share of samples that are deformed."""
     hflip: float = 0.0
     vflip: float = 0.0
     scale: Tuple[float, float] = (1.0, 1.0)
@@ -52,9 +75,12 @@ class SegAugConfig:
     translate: float = 0.0
     prob: float = 1.0
     image_fill: float = 0.0
+    elastic_sigma: float = 0.0
+    elastic_grid: int = 3
+    elastic_prob: float = 1.0
 
     def __post_init__(self):
-        for n in ("hflip", "vflip", "prob"):
+        for n in ("hflip", "vflip", "prob", "elastic_prob"):
             v = getattr(self, n)
             if not 0 <= v <= 1:
                 raise ValueError(f"{n} must lie in [0, 1], got {v}")
@@ -71,6 +97,11 @@ class SegAugConfig:
                 raise ValueError(f"{n} must be finite and >= 0, got {v}")
         if not math.isfinite(self.image_fill):
             raise ValueError(f"image_fill must be finite, got {self.image_fill}")
+        if not 0 <= self.elastic_sigma <= MAX_SIGMA:       # (NaN fails the comparison too)
+            raise ValueError(f"elastic_sigma must lie in [0, {MAX_SIGMA}], got {self.elastic_sigma}")
+        if int(self.elastic_grid) != self.elastic_grid or not 1 <= self.elastic_grid <= MAX_GRID:
+            raise ValueError(f"elastic_grid must be an integer in [1, {MAX_GRID}], got {self.elastic_grid}")
+        object.__setattr__(self, "elastic_grid", int(self.elastic_grid))
 
     @property
     def enabled(self) -> bool:
@@ -129,6 +160,51 @@ def draw_seg_aug(cfg: SegAugConfig, seed: int, epoch: int, N: int, H: int, W: in
     return _affine_q16(H, W, Ho, Wo, p["hflip"], p["vflip"], p["scale"], p["degrees"], p["tx"], p["ty"]).reshape(N, 6)
 
 
+def seg_elastic_axis(n: int, G: int) -> np.ndarray:
+    """The axis table of ``n`` output pixels over ``G`` cells: int32 [n, 5], rows ``(i, w0, w1, w2, w3)``.  Pixel
+    centre ``p + 0.5`` lies in cell ``i = ((2p + 1) G) // (2n)`` at ``t = (((2p + 1) G) mod (2n)) / (2n)``; the
+    weights are the cubic B-spline basis at ``t`` rounded to Q20, the rounding's remainder added to the largest
+    (the first such), so that they are >= 0 and sum to 2^20 exactly."""
+    if int(n) != n or n < 1 or int(G) != G or not 1 <= G <= MAX_GRID:
+        raise ValueError(f"n must be an integer >= 1 and G one in [1, {MAX_GRID}], got {n} and {G}")
+    num = (2 * np.arange(int(n), dtype=np.int64) + 1) * int(G)
+    t = (num % (2 * n)) / (2.0 * n)
+    basis = np.stack([(1 - t) ** 3, 3 * t ** 3 - 6 * t ** 2 + 4, -3 * t ** 3 + 3 * t ** 2 + 3 * t + 1, t ** 3], 1) / 6
+    w = np.rint(basis * QW).astype(np.int64)
+    w[np.arange(int(n)), np.argmax(w, axis=1)] += QW - w.sum(1)
+    return np.concatenate([(num // (2 * n))[:, None], w], 1).astype(np.int32)
+
+
+def draw_seg_elastic(cfg: SegAugConfig, seed: int, epoch: int, N: int) -> np.ndarray:
+    """The control lattices of ``epoch``: int32 [N, 2, L, L] in Q16 source pixels, ``L = cfg.elastic_grid + 3``.
+    ``D = rint(clip(z, -4, 4) sigma 65536)`` with standard normals ``z`` from ``default_rng([seed, epoch, 1])``;
+    sample ``i`` keeps its lattice when ``default_rng([seed, epoch, 2]).random(N)[i] < elastic_prob`` and has zeros
+    otherwise.  Both blocks fill row by row, so sample ``i`` depends on ``(seed, epoch, i)`` alone, and neither
+    touches the stream of :func:`draw_seg_params`.  ``sigma`` is the deviation of the control points: the field
+    blends 16 of them and is smoother and smaller."""
+    L = cfg.elastic_grid + 3
+    if cfg.elastic_sigma == 0:
+        return np.zeros((int(N), 2, L, L), dtype=np.int32)
+    z = np.random.default_rng([int(seed), int(epoch), 1]).standard_normal((int(N), 2, L, L))
+    keep = np.random.default_rng([int(seed), int(epoch), 2]).random(int(N)) < cfg.elastic_prob
+    D = np.rint(np.clip(z, -4.0, 4.0) * (cfg.elastic_sigma * Q))
+    return np.where(keep[:, None, None, None], D, 0.0).astype(np.int32)
+
+
+def seg_elastic_field(lattice, ex, ey) -> torch.Tensor:
+    """The displacement of every output pixel: lattice int [B, 2, L, L], ex int [Wo, 5], ey int [Ho, 5] -> int64
+    [B, 2, Ho, Wo] in Q16 (component 0: x).  Columns first, then rows, rounded after each pass; cells are clamped
+    into ``[0, L - 4]`` as the kernel clamps them."""
+    D = torch.as_tensor(np.asarray(lattice)).to(torch.int64)
+    ex, ey = (torch.as_tensor(np.asarray(e)).to(torch.int64) for e in (ex, ey))
+    G = D.shape[-1] - 3
+    four = torch.arange(4)
+    cols = ex[:, :1].clamp(0, G - 1) + four                              # [Wo, 4]
+    E = ((D[:, :, :, cols] * ex[:, 1:]).sum(-1) + QW // 2) >> 20         # [B, 2, L, Wo]
+    rows = ey[:, :1].clamp(0, G - 1) + four                              # [Ho, 4]
+    return ((E[:, :, rows] * ey[:, 1:, None]).sum(3) + QW // 2) >> 20    # [B, 2, Ho, 4, Wo] -> [B, 2, Ho, Wo]
+
+
 def _taps(src, inside, iy, ix, W, fill):
     """src [B, P, H * W] sampled at (iy, ix) [B, Ho * Wo] where ``inside``, ``fill`` elsewhere -> [B, P, Ho * Wo]."""
     flat = torch.where(inside, iy * W + ix, torch.zeros_like(ix))     # no out-of-range index is ever formed
@@ -137,10 +213,13 @@ def _taps(src, inside, iy, ix, W, fill):
     return torch.where(inside.unsqueeze(1), got, fill)
 
 
-def seg_aug_reference(images, masks, idx, table, Ho, Wo, image_fill=0.0, mask_fill=0, dtype=torch.float32):
-    """Torch reference of the batch kernel (and the CPU execution path): images fp32 [N, C, H, W], masks [N, H, W],
+def seg_aug_reference(images, masks, idx, table, Ho, Wo, image_fill=0.0, mask_fill=0, dtype=torch.float32,
+                      lattice=None, grid=None):
+    """Torch reference of the batch kernels (and the CPU execution path): images fp32 [N, C, H, W], masks [N, H, W],
     idx int64 [B], table int32 [N, 6] -> (image ``dtype`` [B, C, Ho, Wo], mask [B, Ho, Wo] of the masks' dtype).
-    ``dtype``: torch.float32 (the device's arithmetic) or torch.float64."""
+    ``dtype``: torch.float32 (the device's arithmetic) or torch.float64.  ``lattice`` int32 [N, 2, grid + 3,
+    grid + 3]: the elastic control points, whose field is added to the coordinates (``grid``: the cells per axis,
+    by default what the lattice's shape says)."""
     idx = torch.as_tensor(idx).to(torch.int64).cpu()
     images, masks = torch.as_tensor(images), torch.as_tensor(masks)
     N, C, H, W = images.shape
@@ -155,6 +234,14 @@ def seg_aug_reference(images, masks, idx, table, Ho, Wo, image_fill=0.0, mask_fi
     ys = torch.arange(Ho, dtype=torch.int64).view(1, Ho, 1)
     X = (a * xs + b * ys + c).reshape(B, Ho * Wo)
     Y = (d * xs + e * ys + f).reshape(B, Ho * Wo)
+    if lattice is not None:
+        lattice = torch.as_tensor(np.asarray(lattice.cpu() if isinstance(lattice, torch.Tensor) else lattice))
+        G = lattice.shape[-1] - 3 if grid is None else int(grid)
+        if tuple(lattice.shape) != (N, 2, G + 3, G + 3):
+            raise ValueError(f"lattice must be [{N}, 2, {G + 3}, {G + 3}], got {tuple(lattice.shape)}")
+        field = seg_elastic_field(lattice[idx], seg_elastic_axis(Wo, G), seg_elastic_axis(Ho, G))
+        X = X + field[:, 0].reshape(B, Ho * Wo)
+        Y = Y + field[:, 1].reshape(B, Ho * Wo)
 
     def inside(iy, ix):
         return (iy >= 0) & (iy < H) & (ix >= 0) & (ix < W)
