@@ -23,6 +23,9 @@ and mask (data/seg_aug.py, DeviceSegDataset); evaluation is unchanged.  --aug_el
 adds the U-Net paper's elastic deformation in that same launch: a cubic B-spline displacement field over
 --aug_elastic_grid cells per axis whose control points are normal with PX source pixels of deviation, for a share
 --aug_elastic_prob of the samples (csrc/kernels/seg_elastic.hip).
+--ohem_ratio R (default 0: off) with --loss ce trains on the hardest pixels of each batch alone (online hard example
+mining, ops.ohem_cross_entropy / ohem_bce_with_logits; --ohem_min_kept, --ohem_thresh): k and the cut are found on
+the device (csrc/kernels/ohem.hip), so the step stays capturable.
 """
 from __future__ import annotations
 
@@ -42,8 +45,8 @@ from .. import parallel
 from ..data import (CarvanaDataset, DeviceBatches, DeviceCachedDataset, DeviceSegDataset, DistributedSampler,
                     SegAugConfig, SyntheticMasks)
 from ..models import UNet
-from ..ops import (BCEDiceLoss, BCEWithLogitsLoss, CEDiceLoss, CrossEntropyLoss, DiceLoss, backward, dice_multiclass,
-                   dice_per_sample)
+from ..ops import (BCEDiceLoss, BCEWithLogitsLoss, CEDiceLoss, CrossEntropyLoss, DiceLoss, OHEMBCEWithLogitsLoss,
+                   OHEMCrossEntropyLoss, backward, dice_multiclass, dice_per_sample)
 from ..optim import LAMB, Adam, clip_grad_norm_
 from ..utils.graphs import CapturedStep
 from ..utils.checkpoint import load_checkpoint, resume_state, save_checkpoint, set_rng_state
@@ -76,6 +79,12 @@ def build_argparser() -> argparse.ArgumentParser:
     p.add_argument("--dice_smooth", type=float, default=1.0, help="smoothing constant of the soft Dice (> 0)")
     p.add_argument("--dice_background", type=int, default=1, choices=[0, 1],
                    help="0: leave class 0 out of the multi-class Dice mean")
+    p.add_argument("--ohem_ratio", type=float, default=0.0, metavar="R",
+                   help="online hard example mining with --loss ce: the loss over the hardest share R of the batch's "
+                        "valid pixels (0: off)")
+    p.add_argument("--ohem_min_kept", type=int, default=1, metavar="N", help="mine at least N pixels")
+    p.add_argument("--ohem_thresh", type=float, default=0.0, metavar="P",
+                   help="also mine every pixel whose label is predicted with a probability below P (0: none)")
     p.add_argument("--data_dir", default="data")
     p.add_argument("--scale", type=float, default=0.2)
     p.add_argument("--up_sample_mode", default="conv_transpose", choices=["conv_transpose", "bilinear"])
@@ -259,9 +268,17 @@ def benchmark(args, train_step, captured, x, y, comm, device) -> dict:
 
 def build_criterion(args):
     """--loss ce (the default): today's BCEWithLogitsLoss / CrossEntropyLoss; dice, ce+dice: the fused soft
-    Dice losses, sigmoid form for --num_classes 1, softmax form (honouring --ignore_index) for K > 1."""
+    Dice losses, sigmoid form for --num_classes 1, softmax form (honouring --ignore_index) for K > 1.
+    --ohem_ratio > 0 (with --loss ce only): the same two over the hardest pixels."""
     K = args.num_classes
     kind = getattr(args, "loss", "ce")   # (callers that build the namespace themselves)
+    ratio = getattr(args, "ohem_ratio", 0.0)
+    if ratio != 0:
+        if kind != "ce":
+            raise ValueError(f"--ohem_ratio mines the pixels of --loss ce; it does not go with --loss {kind}")
+        sel = dict(keep_ratio=ratio, min_kept=getattr(args, "ohem_min_kept", 1),
+                   thresh=getattr(args, "ohem_thresh", 0.0) or None)
+        return OHEMCrossEntropyLoss(ignore_index=args.ignore_index, **sel) if K > 1 else OHEMBCEWithLogitsLoss(**sel)
     if kind == "ce":
         return CrossEntropyLoss(ignore_index=args.ignore_index) if K > 1 else BCEWithLogitsLoss()
     if kind not in ("dice", "ce+dice"):
@@ -438,6 +455,10 @@ def parse_args(argv=None):
         p.error(f"--num_classes must be >= 1, got {args.num_classes}")
     check_layerwise_args(p, args, "adam")
     check_ema_args(p, args)
+    try:
+        build_criterion(args)
+    except ValueError as e:
+        p.error(str(e))
     try:
         aug = seg_aug_config(args)
     except ValueError as e:

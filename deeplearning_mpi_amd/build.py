@@ -33,7 +33,8 @@ C_SO = os.path.join(HERE, "_C" + EXT_SUFFIX)
 MPI_SO = os.path.join(HERE, "_mpi" + EXT_SUFFIX)
 
 # hipcc flags of single kernel files: scalar fp32 only (no packed v_pk_*_f32) where every lerp is rounded on its own
-FILE_FLAGS = {"seg_elastic.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+_SCALAR_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+FILE_FLAGS = {"seg_elastic.hip": _SCALAR_F32, "ohem.hip": _SCALAR_F32}
 
 
 def _headers():

@@ -1,4 +1,5 @@
-// Torch binding of the losses and evaluation counts (kernels/loss.hip, cls_ce.hip, pixel_ce.hip, seg_dice.hip).
+// Torch binding of the losses and evaluation counts (kernels/loss.hip, cls_ce.hip, pixel_ce.hip, seg_dice.hip,
+// ohem.hip).
 // softmax_ce_*, bce_*, argmax_correct and dice take their shapes from the caller (NativeBackend) unchecked.
 #include <algorithm>
 #include <cmath>
@@ -245,6 +246,98 @@ void bce_dice_bwd(const at::Tensor& logits, const at::Tensor& target, int N, int
                            (float)bce_weight, ptr<float>(dlogits), cur_stream()),
         "bce_dice_bwd");
 }
+// Online hard example mining (ohem.hip).  The selection's parameters are checked here, host-side; tau = -log(thresh)
+// is formed in double and rounded once to fp32.  state: int32 [8] = {k, n_valid, n_selected, the bits of cut, ...};
+// the histograms and the partial sums are allocated here as pixel_ce_fwd's partials are.
+struct OhemParams {
+  int has_tau;
+  float tau;
+  at::Tensor ws, partial;
+};
+OhemParams ohem_params(const char* fn, double keep_ratio, int64_t min_kept, const c10::optional<double>& tau,
+                       int64_t M, const at::Tensor& like, const at::Tensor& state) {
+  if (!(keep_ratio > 0 && keep_ratio <= 1)) fail(fn, "keep_ratio must lie in (0, 1]");
+  if (min_kept < 1) fail(fn, "min_kept must be >= 1");
+  if (tau.has_value() && !(*tau > 0 && std::isfinite(*tau) && (float)*tau > 0))
+    fail(fn, "thresh must lie in (0, 1) (tau = -log(thresh) finite and > 0)");
+  if (M < 1 || M > 2147483647LL) fail(fn, "the selection counts in uint32: 1 <= pixels < 2^31");
+  dense(state, at::kInt, 8, fn, "state");
+  return {tau.has_value() ? 1 : 0, tau.has_value() ? (float)*tau : 0.f,
+          at::empty({(int64_t)dlmpi_ohem_ws_words()}, like.options().dtype(at::kInt)),
+          at::empty({(int64_t)dlmpi_ohem_partial_floats(M)}, like.options().dtype(at::kFloat))};
+}
+c10::optional<double> ohem_tau(const char* fn, const c10::optional<double>& thresh) {
+  if (!thresh.has_value()) return c10::nullopt;
+  if (!(*thresh > 0 && *thresh < 1)) fail(fn, "thresh must lie in (0, 1)");
+  return -std::log(*thresh);
+}
+void ohem_select(const at::Tensor& nll, double keep_ratio, int64_t min_kept, const c10::optional<double>& tau,
+                 at::Tensor state, at::Tensor loss, at::Tensor den) {
+  if (layout_fault(nll, at::kFloat) != Fault::none) fail("ohem_select", "nll must be a contiguous fp32 GPU tensor");
+  OhemParams p = ohem_params("ohem_select", keep_ratio, min_kept, tau, nll.numel(), nll, state);
+  dense(loss, at::kFloat, 1, "ohem_select", "loss");
+  dense(den, at::kFloat, 1, "ohem_select", "den");
+  check(dlmpi_ohem_select(ptr<float>(nll), nll.numel(), keep_ratio, min_kept, p.has_tau, p.tau, ptr<uint32_t>(p.ws),
+                          ptr<float>(p.partial), ptr<uint32_t>(state), ptr<float>(loss), ptr<float>(den),
+                          cur_stream()),
+        "ohem_select");
+}
+void ohem_ce_fwd(const at::Tensor& logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                 const at::Tensor& labels, int64_t ignore_index, const c10::optional<at::Tensor>& weight,
+                 double keep_ratio, int64_t min_kept, const c10::optional<double>& thresh, at::Tensor lse,
+                 at::Tensor nll, at::Tensor state, at::Tensor loss, at::Tensor den) {
+  pix_fwd_check("ohem_ce_fwd", logits, sn, sk, sp, N, K, HW, labels, weight, lse, den, nullptr, &loss);
+  dense(nll, at::kFloat, (int64_t)N * HW, "ohem_ce_fwd", "nll");
+  OhemParams p = ohem_params("ohem_ce_fwd", keep_ratio, min_kept, ohem_tau("ohem_ce_fwd", thresh), (int64_t)N * HW,
+                             logits, state);
+  check(dlmpi_ohem_ce_fwd(ptr<float>(logits), sn, sk, sp, N, K, HW, ptr<int64_t>(labels), ignore_index,
+                          optr<float>(weight), keep_ratio, min_kept, p.has_tau, p.tau, ptr<float>(lse),
+                          ptr<float>(nll), ptr<uint32_t>(p.ws), ptr<float>(p.partial), ptr<uint32_t>(state),
+                          ptr<float>(loss), ptr<float>(den), cur_stream()),
+        "ohem_ce_fwd");
+}
+void ohem_ce_bwd(const at::Tensor& logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                 const at::Tensor& labels, int64_t ignore_index, const c10::optional<at::Tensor>& weight,
+                 const at::Tensor& lse, const at::Tensor& nll, const at::Tensor& cut,
+                 const c10::optional<at::Tensor>& go, const at::Tensor& den, at::Tensor dlogits) {
+  pix_bwd_check("ohem_ce_bwd", logits, sn, sk, sp, N, K, HW, labels, weight, lse, den, nullptr, dlogits, go);
+  dense(nll, at::kFloat, (int64_t)N * HW, "ohem_ce_bwd", "nll");
+  dense(cut, at::kFloat, 1, "ohem_ce_bwd", "cut");
+  check(dlmpi_ohem_ce_bwd(ptr<float>(logits), sn, sk, sp, N, K, HW, ptr<int64_t>(labels), ignore_index,
+                          optr<float>(weight), ptr<float>(lse), ptr<float>(nll), ptr<float>(cut), optr<float>(go),
+                          ptr<float>(den), ptr<float>(dlogits), cur_stream()),
+        "ohem_ce_bwd");
+}
+// logits, target: contiguous fp32 of M elements
+void ohem_bce_fwd(const at::Tensor& logits, const at::Tensor& target, int64_t M, double keep_ratio, int64_t min_kept,
+                  const c10::optional<double>& thresh, at::Tensor nll, at::Tensor state, at::Tensor loss,
+                  at::Tensor den) {
+  OhemParams p = ohem_params("ohem_bce_fwd", keep_ratio, min_kept, ohem_tau("ohem_bce_fwd", thresh), M, logits, state);
+  dense(logits, at::kFloat, M, "ohem_bce_fwd", "logits");
+  dense(target, at::kFloat, M, "ohem_bce_fwd", "target");
+  dense(nll, at::kFloat, M, "ohem_bce_fwd", "nll");
+  dense(loss, at::kFloat, 1, "ohem_bce_fwd", "loss");
+  dense(den, at::kFloat, 1, "ohem_bce_fwd", "den");
+  check(dlmpi_ohem_bce_fwd(ptr<float>(logits), ptr<float>(target), M, keep_ratio, min_kept, p.has_tau, p.tau,
+                           ptr<float>(nll), ptr<uint32_t>(p.ws), ptr<float>(p.partial), ptr<uint32_t>(state),
+                           ptr<float>(loss), ptr<float>(den), cur_stream()),
+        "ohem_bce_fwd");
+}
+void ohem_bce_bwd(const at::Tensor& logits, const at::Tensor& target, int64_t M, const at::Tensor& nll,
+                  const at::Tensor& cut, const c10::optional<at::Tensor>& go, const at::Tensor& den,
+                  at::Tensor dlogits) {
+  if (M < 1 || M > 2147483647LL) fail("ohem_bce_bwd", "1 <= pixels < 2^31");
+  dense(logits, at::kFloat, M, "ohem_bce_bwd", "logits");
+  dense(target, at::kFloat, M, "ohem_bce_bwd", "target");
+  dense(nll, at::kFloat, M, "ohem_bce_bwd", "nll");
+  dense(dlogits, at::kFloat, M, "ohem_bce_bwd", "dlogits");
+  dense(cut, at::kFloat, 1, "ohem_bce_bwd", "cut");
+  dense(den, at::kFloat, 1, "ohem_bce_bwd", "den");
+  dense(go, at::kFloat, 1, "ohem_bce_bwd", "go");
+  check(dlmpi_ohem_bce_bwd(ptr<float>(logits), ptr<float>(target), M, ptr<float>(nll), ptr<float>(cut),
+                           optr<float>(go), ptr<float>(den), ptr<float>(dlogits), cur_stream()),
+        "ohem_bce_bwd");
+}
 }  // namespace
 
 void register_loss(pybind11::module& m) {
@@ -271,6 +364,12 @@ void register_loss(pybind11::module& m) {
   m.def("pixel_ce_dice_bwd", &pixel_ce_dice_bwd);
   m.def("bce_dice_fwd", &bce_dice_fwd);
   m.def("bce_dice_bwd", &bce_dice_bwd);
+  m.def("ohem_select", &ohem_select);
+  m.def("ohem_ce_fwd", &ohem_ce_fwd);
+  m.def("ohem_ce_bwd", &ohem_ce_bwd);
+  m.def("ohem_bce_fwd", &ohem_bce_fwd);
+  m.def("ohem_bce_bwd", &ohem_bce_bwd);
+  m.def("set_ohem_aggregate", [](int on) { dlmpi_set_ohem_aggregate(on); });
 }
 
 }  // namespace dlmpi_ext

@@ -454,6 +454,32 @@ hipError_t dlmpi_bce_dice_fwd(const float* logits, const float* target, int N, i
                               float dice_weight, float smooth, float* part, float* loss, float* tab, hipStream_t s);
 hipError_t dlmpi_bce_dice_bwd(const float* logits, const float* target, int N, int64_t HW, const float* go,
                               const float* tab, float bce_weight, float* dlogits, hipStream_t s);
+// Online hard example mining (ohem.hip): the loss over S = {valid m : l_m >= cut}, cut = the k-th largest l (or
+// min(tau, that) with has_tau), k = min(n_valid, max(min_kept, ceil(keep_ratio * n_valid))) formed on the device.
+// keep_ratio in (0, 1], min_kept >= 1, tau > 0, N * HW < 2^31.  nll [M]: l, negative where not valid; ws:
+// dlmpi_ohem_ws_words() uint32, zeroed here; partial: dlmpi_ohem_partial_floats(M) floats; state uint32 [8] =
+// {k, n_valid, n_selected, the bits of cut, 4 words of the chain's own}.  No host read, no float atomics.
+int dlmpi_ohem_ws_words();
+int dlmpi_ohem_partial_floats(int64_t M);
+void dlmpi_set_ohem_aggregate(int on);   // 1: wave-level aggregation of the histogram atomics (A/B)
+// the selection alone on a caller's nll (sign bit = not valid); loss = the mean of S, den = |S|
+hipError_t dlmpi_ohem_select(const float* nll, int64_t M, double keep_ratio, int64_t min_kept, int has_tau, float tau,
+                             uint32_t* ws, float* partial, uint32_t* state, float* loss, float* den, hipStream_t s);
+hipError_t dlmpi_ohem_ce_fwd(const float* logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                             const int64_t* labels, int64_t ignore_index, const float* weight, double keep_ratio,
+                             int64_t min_kept, int has_tau, float tau, float* lse, float* nll, uint32_t* ws,
+                             float* partial, uint32_t* state, float* loss, float* den, hipStream_t s);
+// cut: the float at state + 3; pixel_ce_bwd's gradient on S, exact zeros elsewhere
+hipError_t dlmpi_ohem_ce_bwd(const float* logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                             const int64_t* labels, int64_t ignore_index, const float* weight, const float* lse,
+                             const float* nll, const float* cut, const float* go, const float* den, float* dlogits,
+                             hipStream_t s);
+// binary form: contiguous logits / float targets [M], every pixel valid
+hipError_t dlmpi_ohem_bce_fwd(const float* logits, const float* target, int64_t M, double keep_ratio,
+                              int64_t min_kept, int has_tau, float tau, float* nll, uint32_t* ws, float* partial,
+                              uint32_t* state, float* loss, float* den, hipStream_t s);
+hipError_t dlmpi_ohem_bce_bwd(const float* logits, const float* target, int64_t M, const float* nll, const float* cut,
+                              const float* go, const float* den, float* dlogits, hipStream_t s);
 
 // eval
 hipError_t dlmpi_argmax_correct(const float* logits, int ldl, const int64_t* labels, int N, int K, int* correct,

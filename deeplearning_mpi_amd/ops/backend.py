@@ -11,6 +11,7 @@ Both expose the same methods; the engine (models/*) is written once against this
 """
 from __future__ import annotations
 
+import math
 import os
 import weakref
 import struct
@@ -549,6 +550,56 @@ class NativeBackend:
         self.C.bce_dice_bwd(logits, target, logits.shape[0], logits[0].numel(), go, tab, float(bce_weight), d)
         return d
 
+    # online hard example mining (ohem.hip): stats = {cut, k, n_valid, n_selected}, 1-element views of one device
+    # vector that nothing here reads
+    @staticmethod
+    def _ohem_stats(state):
+        return {"cut": state[3:4].view(torch.float32), "k": state[0:1], "n_valid": state[1:2],
+                "n_selected": state[2:3]}
+
+    def _ohem_out(self, like):   # state int32 [8], loss (scalar), den [1]
+        state = torch.empty(8, dtype=torch.int32, device=like.device)
+        return state, torch.empty((), dtype=torch.float32, device=like.device), \
+            torch.empty(1, dtype=torch.float32, device=like.device)
+
+    def ohem_select(self, nll, keep_ratio, min_kept=1, tau=None):
+        """The selection alone over fp32 ``nll`` (sign bit set: not valid): stats, with ``loss`` = the mean of the
+        selected values."""
+        state, loss, den = self._ohem_out(nll)
+        self.C.ohem_select(nll, float(keep_ratio), int(min_kept), None if tau is None else float(tau), state, loss,
+                           den)
+        return dict(self._ohem_stats(state), loss=loss)
+
+    def ohem_ce_fwd(self, logits, labels, weight=None, ignore_index=-100, keep_ratio=0.25, min_kept=1, thresh=None):
+        """pixel_ce_fwd over the hardest pixels -> (loss, lse [N*H*W], nll [N*H*W] (-1: ignored), den, stats)."""
+        N, K, H, W = logits.shape
+        lse, loss, den = self._pixel_fwd_out(logits)
+        nll, state = torch.empty_like(lse), torch.empty(8, dtype=torch.int32, device=logits.device)
+        self.C.ohem_ce_fwd(logits, *pixel_strides(logits), N, K, H * W, labels, int(ignore_index), weight,
+                           float(keep_ratio), int(min_kept), None if thresh is None else float(thresh), lse, nll,
+                           state, loss, den)
+        return loss, lse, nll, den, self._ohem_stats(state)
+
+    def ohem_ce_bwd(self, logits, labels, lse, nll, cut, den, go, weight=None, ignore_index=-100):
+        N, K, H, W = logits.shape
+        d = self._pixel_dlogits(logits)
+        self.C.ohem_ce_bwd(logits, *pixel_strides(logits), N, K, H * W, labels, int(ignore_index), weight, lse, nll,
+                           cut, go, den, d)
+        return d
+
+    def ohem_bce_fwd(self, logits, target, keep_ratio=0.25, min_kept=1, thresh=None):
+        """logits, target fp32 contiguous, every pixel valid -> (loss, nll, den = |S|, stats)."""
+        state, loss, den = self._ohem_out(logits)
+        nll = torch.empty(logits.numel(), dtype=torch.float32, device=logits.device)
+        self.C.ohem_bce_fwd(logits, target, logits.numel(), float(keep_ratio), int(min_kept),
+                            None if thresh is None else float(thresh), nll, state, loss, den)
+        return loss, nll, den, self._ohem_stats(state)
+
+    def ohem_bce_bwd(self, logits, target, nll, cut, den, go):
+        d = torch.empty_like(logits, memory_format=torch.contiguous_format)
+        self.C.ohem_bce_bwd(logits, target, logits.numel(), nll, cut, go, den, d)
+        return d
+
     def bce_fwd(self, logits, target):
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
         self.C.bce_fwd(logits, 1, target, logits.numel(), loss)
@@ -1085,6 +1136,72 @@ class RefBackend:
         if bce_weight != 0:
             d = d + (p - t) * (bce_weight * go / x.numel())
         return d.view(logits.shape)
+
+    # online hard example mining: the k-th largest by kthvalue on the valid values, the same >= rule
+    def _ohem_pick(self, nll, keep_ratio, min_kept, tau):
+        """nll flat (negative: not valid) -> (selection mask, stats); the rules of csrc/kernels/ohem.hip."""
+        if not 0 < keep_ratio <= 1:
+            raise ValueError(f"keep_ratio must lie in (0, 1], got {keep_ratio}")
+        if min_kept < 1:
+            raise ValueError(f"min_kept must be >= 1, got {min_kept}")
+        valid = ~(nll < 0)   # a NaN is valid, and the largest
+        v = nll[valid]
+        nv = v.numel()
+        k = min(nv, max(int(min_kept), math.ceil(keep_ratio * nv)))
+        cut = nll.new_zeros(())
+        if nv:
+            cut = torch.kthvalue(v, nv - k + 1).values
+            if tau is not None:
+                t = torch.tensor(tau, dtype=torch.float32).to(nll.dtype)
+                cut = t if torch.isnan(cut) else torch.minimum(cut, t)
+        sel = valid & ((nll >= cut) | torch.isnan(nll))
+        i32 = dict(dtype=torch.int32, device=nll.device)
+        return sel, {"cut": cut.reshape(1), "k": torch.tensor([k], **i32), "n_valid": torch.tensor([nv], **i32),
+                     "n_selected": sel.sum().to(torch.int32).reshape(1)}
+
+    @staticmethod
+    def _ohem_tau(thresh):
+        if thresh is None:
+            return None
+        if not 0 < thresh < 1:
+            raise ValueError(f"thresh must lie in (0, 1), got {thresh}")
+        return float(torch.tensor(-math.log(thresh), dtype=torch.float32))   # rounded once to fp32
+
+    def ohem_select(self, nll, keep_ratio, min_kept=1, tau=None):
+        sel, stats = self._ohem_pick(nll, keep_ratio, min_kept, tau)
+        return dict(stats, loss=nll[sel].sum() / sel.sum())
+
+    def ohem_ce_fwd(self, logits, labels, weight=None, ignore_index=-100, keep_ratio=0.25, min_kept=1, thresh=None):
+        x = logits.to(self.dt)
+        K = x.shape[1]
+        keep = self._pix_keep(labels, K, ignore_index).reshape(-1)
+        t = labels.clamp(0, K - 1)
+        lse = torch.logsumexp(x, 1).reshape(-1)
+        l = (lse - x.gather(1, t.unsqueeze(1)).reshape(-1)).clamp_min(0)   # (clamp_min keeps a NaN)
+        nll = torch.where(keep, l, -torch.ones_like(l))
+        sel, stats = self._ohem_pick(nll, keep_ratio, min_kept, self._ohem_tau(thresh))
+        w = weight.to(self.dt)[t.reshape(-1)] if weight is not None else torch.ones_like(l)
+        den = (w * sel).sum().reshape(1)
+        loss = (torch.where(sel, w * l, torch.zeros_like(l)).sum() / den).reshape(())
+        return loss, lse, nll, den, stats
+
+    def ohem_ce_bwd(self, logits, labels, lse, nll, cut, den, go, weight=None, ignore_index=-100):
+        sel = ~(nll < 0) & ((nll >= cut) | torch.isnan(nll))
+        d = self.pixel_ce_bwd(logits, labels, lse, den, go, weight, ignore_index)
+        N, K, H, W = logits.shape
+        return torch.where(sel.view(N, 1, H, W), d, torch.zeros((), dtype=self.dt, device=d.device))
+
+    def ohem_bce_fwd(self, logits, target, keep_ratio=0.25, min_kept=1, thresh=None):
+        x, t = logits.to(self.dt).reshape(-1), target.to(self.dt).reshape(-1)
+        nll = F.binary_cross_entropy_with_logits(x, t, reduction="none").clamp_min(0)
+        sel, stats = self._ohem_pick(nll, keep_ratio, min_kept, self._ohem_tau(thresh))
+        den = sel.sum().to(self.dt).reshape(1)
+        return (torch.where(sel, nll, torch.zeros_like(nll)).sum() / den).reshape(()), nll, den, stats
+
+    def ohem_bce_bwd(self, logits, target, nll, cut, den, go):
+        sel = ((nll >= cut) | torch.isnan(nll)).view(logits.shape)
+        d = (torch.sigmoid(logits.to(self.dt)) - target) * (go if go is not None else 1.0) / den
+        return torch.where(sel, d, torch.zeros((), dtype=self.dt, device=d.device))
 
     def bce_fwd(self, logits, target):
         return F.binary_cross_entropy_with_logits(logits.to(self.dt), target.to(self.dt))

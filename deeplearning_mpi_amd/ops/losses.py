@@ -190,6 +190,104 @@ def bce_with_logits(logits, target):
     return _BCE.apply(logits, target)
 
 
+_OHEM_STATS = ("cut", "k", "n_valid", "n_selected")
+
+
+class _OhemCE(torch.autograd.Function):
+    """:class:`_PixelCE` over the hardest pixels (csrc/kernels/ohem.hip): logits read in place, the gradient in
+    their strides; returns the loss and the four device statistics (not differentiable, never read here)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, ignore_index, keep_ratio, min_kept, thresh):
+        be, x, labels, w = _pixel_inputs(logits, labels, weight)
+        loss, lse, nll, den, st = be.ohem_ce_fwd(x, labels, w, ignore_index, keep_ratio, min_kept, thresh)
+        ctx.save_for_backward(x, labels, lse, nll, st["cut"], den, w)
+        ctx.ignore_index, ctx.in_dtype = ignore_index, logits.dtype
+        stats = tuple(st[n] for n in _OHEM_STATS)
+        ctx.mark_non_differentiable(*stats)
+        return (loss,) + stats
+
+    @staticmethod
+    def backward(ctx, go, *_):
+        x, labels, lse, nll, cut, den, w = ctx.saved_tensors
+        be = _be(x.device, x.dtype)
+        g = be.ohem_ce_bwd(x, labels, lse, nll, cut, den, go.reshape(1).to(be.dt).contiguous(), w, ctx.ignore_index)
+        return (g.to(ctx.in_dtype),) + (None,) * 6
+
+
+class _OhemBCE(torch.autograd.Function):
+    """BCE-with-logits over the hardest pixels: contiguous logits and float targets of one shape."""
+
+    @staticmethod
+    def forward(ctx, logits, target, keep_ratio, min_kept, thresh):
+        be = _be(logits.device, logits.dtype)
+        x = logits.contiguous().to(be.dt)
+        target = target.contiguous().to(be.dt)
+        loss, nll, den, st = be.ohem_bce_fwd(x, target, keep_ratio, min_kept, thresh)
+        ctx.save_for_backward(x, target, nll, st["cut"], den)
+        ctx.in_dtype = logits.dtype
+        stats = tuple(st[n] for n in _OHEM_STATS)
+        ctx.mark_non_differentiable(*stats)
+        return (loss,) + stats
+
+    @staticmethod
+    def backward(ctx, go, *_):
+        x, target, nll, cut, den = ctx.saved_tensors
+        be = _be(x.device, x.dtype)
+        g = be.ohem_bce_bwd(x, target, nll, cut, den, go.reshape(1).to(be.dt).contiguous())
+        return g.view(x.shape).to(ctx.in_dtype), None, None, None, None
+
+
+def _check_ohem_args(keep_ratio, min_kept, thresh):
+    keep_ratio, min_kept = float(keep_ratio), int(min_kept)
+    if not 0 < keep_ratio <= 1:
+        raise ValueError(f"keep_ratio must lie in (0, 1], got {keep_ratio}")
+    if min_kept < 1:
+        raise ValueError(f"min_kept must be >= 1, got {min_kept}")
+    if thresh is not None and not 0 < float(thresh) < 1:
+        raise ValueError(f"thresh must be None or a probability in (0, 1), got {thresh}")
+    return keep_ratio, min_kept, None if thresh is None else float(thresh)
+
+
+def _ohem_ce(logits, labels, weight, ignore_index, keep_ratio, min_kept, thresh):
+    sel = _check_ohem_args(keep_ratio, min_kept, thresh)
+    if logits.dim() != 4:
+        raise ValueError(f"ohem_cross_entropy takes [N, K, H, W] logits, got {tuple(logits.shape)}")
+    _check_pixel_args(logits, labels, weight)
+    out = _OhemCE.apply(logits, labels, weight, int(ignore_index), *sel)
+    return out[0], dict(zip(_OHEM_STATS, out[1:]))
+
+
+def _ohem_bce(logits, target, keep_ratio, min_kept, thresh):
+    sel = _check_ohem_args(keep_ratio, min_kept, thresh)
+    if logits.dim() == target.dim() + 1 and logits.shape[1] == 1:
+        logits = logits.squeeze(1)
+    if target.dim() < 2 or logits.shape != target.shape or not target.is_floating_point():
+        raise ValueError(f"ohem_bce_with_logits takes logits [N, H, W] or [N, 1, H, W] and a float target [N, H, W], "
+                         f"got {tuple(logits.shape)} and {target.dtype} {tuple(target.shape)}")
+    out = _OhemBCE.apply(logits, target, *sel)
+    return out[0], dict(zip(_OHEM_STATS, out[1:]))
+
+
+def ohem_cross_entropy(logits, labels, weight=None, ignore_index=-100, keep_ratio=0.25, min_kept=1, thresh=None):
+    """Pixel-wise cross-entropy over the hardest pixels of the batch (online hard example mining) for
+    [N, K, H, W] logits and int64 [N, H, W] labels.  With l_m = max(0, lse_m - x_m[t_m]) over the kept pixels (as
+    :func:`cross_entropy`) and n_valid their number: k = min(n_valid, max(min_kept, ceil(keep_ratio * n_valid))),
+    cut = the k-th largest l, or min(-log(thresh), that) with ``thresh`` (a probability: pixels predicted below
+    it are always mined), S = {kept m : l_m >= cut} -- every tie at the cut included, so the set depends on no
+    order -- and loss = sum_S w[t] l / sum_S w[t].  ``weight`` enters the sums only, the selection is on the
+    unweighted l.  Pixels outside S get an exact zero gradient.  On the GPU k and the cut are found on the device
+    by an exact radix select (csrc/kernels/ohem.hip): no host synchronisation, the same bits on every run, and
+    ``keep_ratio=1, min_kept=1`` is :func:`cross_entropy`'s loss."""
+    return _ohem_ce(logits, labels, weight, ignore_index, keep_ratio, min_kept, thresh)[0]
+
+
+def ohem_bce_with_logits(logits, target, keep_ratio=0.25, min_kept=1, thresh=None):
+    """The binary form of :func:`ohem_cross_entropy` for logits [N, H, W] or [N, 1, H, W] and a float target
+    [N, H, W]: l = max(x, 0) - x t + log1p(exp(-|x|)), every pixel valid, loss = the mean of l over S."""
+    return _ohem_bce(logits, target, keep_ratio, min_kept, thresh)[0]
+
+
 class _PixelCEDice(torch.autograd.Function):
     """ce_weight * pixel-wise cross-entropy + dice_weight * soft Dice in the passes of _PixelCE: one fused
     forward, one finish, one fused backward; logits read in place, gradient in their strides."""
@@ -334,6 +432,36 @@ class CrossEntropyLoss(nn.Module):
 class BCEWithLogitsLoss(nn.Module):
     def forward(self, logits, target):
         return bce_with_logits(logits, target)
+
+
+class OHEMCrossEntropyLoss(nn.Module):
+    """:func:`ohem_cross_entropy`; ``last_stats`` holds the latest forward's device tensors ``cut`` (fp32), ``k``,
+    ``n_valid`` and ``n_selected`` (int32), one element each, which the library itself never reads."""
+
+    def __init__(self, weight=None, ignore_index=-100, keep_ratio=0.25, min_kept=1, thresh=None):
+        super().__init__()
+        self.register_buffer("weight", weight)
+        self.ignore_index = ignore_index
+        self.keep_ratio, self.min_kept, self.thresh = _check_ohem_args(keep_ratio, min_kept, thresh)
+        self.last_stats = None
+
+    def forward(self, logits, labels):
+        loss, self.last_stats = _ohem_ce(logits, labels, self.weight, self.ignore_index, self.keep_ratio,
+                                         self.min_kept, self.thresh)
+        return loss
+
+
+class OHEMBCEWithLogitsLoss(nn.Module):
+    """:func:`ohem_bce_with_logits`; ``last_stats`` as :class:`OHEMCrossEntropyLoss`."""
+
+    def __init__(self, keep_ratio=0.25, min_kept=1, thresh=None):
+        super().__init__()
+        self.keep_ratio, self.min_kept, self.thresh = _check_ohem_args(keep_ratio, min_kept, thresh)
+        self.last_stats = None
+
+    def forward(self, logits, target):
+        loss, self.last_stats = _ohem_bce(logits, target, self.keep_ratio, self.min_kept, self.thresh)
+        return loss
 
 
 @torch.no_grad()
