@@ -26,6 +26,10 @@ adds the U-Net paper's elastic deformation in that same launch: a cubic B-spline
 --ohem_ratio R (default 0: off) with --loss ce trains on the hardest pixels of each batch alone (online hard example
 mining, ops.ohem_cross_entropy / ohem_bce_with_logits; --ohem_min_kept, --ohem_thresh): k and the cut are found on
 the device (csrc/kernels/ohem.hip), so the step stays capturable.
+--loss lovasz / ce+lovasz trains on the Lovasz extension of the Jaccard loss, alone or added to the plain CE / BCE
+(ops.lovasz_softmax / ce_lovasz_loss for K > 1, ops.lovasz_hinge / bce_lovasz_loss for --num_classes 1;
+--lovasz_weight, --lovasz_per_image, --lovasz_classes): the pixels of every class are ranked by a segmented radix
+sort on the device (csrc/kernels/lovasz.hip), so the step stays capturable.
 """
 from __future__ import annotations
 
@@ -45,8 +49,9 @@ from .. import parallel
 from ..data import (CarvanaDataset, DeviceBatches, DeviceCachedDataset, DeviceSegDataset, DistributedSampler,
                     SegAugConfig, SyntheticMasks)
 from ..models import UNet
-from ..ops import (BCEDiceLoss, BCEWithLogitsLoss, CEDiceLoss, CrossEntropyLoss, DiceLoss, OHEMBCEWithLogitsLoss,
-                   OHEMCrossEntropyLoss, backward, dice_multiclass, dice_per_sample)
+from ..ops import (BCEDiceLoss, BCELovaszLoss, BCEWithLogitsLoss, CEDiceLoss, CELovaszLoss, CrossEntropyLoss, DiceLoss,
+                   LovaszHingeLoss, LovaszSoftmaxLoss, OHEMBCEWithLogitsLoss, OHEMCrossEntropyLoss, backward,
+                   dice_multiclass, dice_per_sample)
 from ..optim import LAMB, Adam, clip_grad_norm_
 from ..utils.graphs import CapturedStep
 from ..utils.checkpoint import load_checkpoint, resume_state, save_checkpoint, set_rng_state
@@ -72,9 +77,15 @@ def build_argparser() -> argparse.ArgumentParser:
                         "logits per pixel, pixel-wise cross-entropy on the mask's class indices")
     p.add_argument("--ignore_index", type=int, default=-100,
                    help="label left out of the multi-class loss and Dice (--num_classes > 1)")
-    p.add_argument("--loss", default="ce", choices=["ce", "dice", "ce+dice"],
+    p.add_argument("--loss", default="ce", choices=["ce", "dice", "ce+dice", "lovasz", "ce+lovasz"],
                    help="ce: BCEWithLogits (--num_classes 1) / pixel-wise cross-entropy (K > 1); dice: the soft Dice "
-                        "loss of sigmoid / softmax; ce+dice: their sum, computed in the passes of ce alone")
+                        "loss of sigmoid / softmax; ce+dice: their sum, computed in the passes of ce alone; lovasz: "
+                        "the Lovasz hinge (--num_classes 1) / Lovasz-Softmax (K > 1) loss; ce+lovasz: ce plus that")
+    p.add_argument("--lovasz_weight", type=float, default=1.0, help="weight of the Lovasz term (--loss ce+lovasz)")
+    p.add_argument("--lovasz_per_image", type=int, default=None, choices=[0, 1],
+                   help="1: rank every sample on its own (default: 1 for --num_classes 1, 0 for K > 1)")
+    p.add_argument("--lovasz_classes", default="present", choices=["present", "all"],
+                   help="average the classes present in the labels, or all of them (K > 1)")
     p.add_argument("--dice_weight", type=float, default=1.0, help="weight of the Dice term (--loss ce+dice)")
     p.add_argument("--dice_smooth", type=float, default=1.0, help="smoothing constant of the soft Dice (> 0)")
     p.add_argument("--dice_background", type=int, default=1, choices=[0, 1],
@@ -268,8 +279,8 @@ def benchmark(args, train_step, captured, x, y, comm, device) -> dict:
 
 def build_criterion(args):
     """--loss ce (the default): today's BCEWithLogitsLoss / CrossEntropyLoss; dice, ce+dice: the fused soft
-    Dice losses, sigmoid form for --num_classes 1, softmax form (honouring --ignore_index) for K > 1.
-    --ohem_ratio > 0 (with --loss ce only): the same two over the hardest pixels."""
+    Dice losses, sigmoid form for --num_classes 1, softmax form (honouring --ignore_index) for K > 1; lovasz,
+    ce+lovasz: the Lovasz hinge / Lovasz-Softmax loss, alone or added to ce.  --ohem_ratio > 0 (with --loss ce only): the same two over the hardest pixels."""
     K = args.num_classes
     kind = getattr(args, "loss", "ce")   # (callers that build the namespace themselves)
     ratio = getattr(args, "ohem_ratio", 0.0)
@@ -281,8 +292,17 @@ def build_criterion(args):
         return OHEMCrossEntropyLoss(ignore_index=args.ignore_index, **sel) if K > 1 else OHEMBCEWithLogitsLoss(**sel)
     if kind == "ce":
         return CrossEntropyLoss(ignore_index=args.ignore_index) if K > 1 else BCEWithLogitsLoss()
+    if kind in ("lovasz", "ce+lovasz"):
+        per_image = getattr(args, "lovasz_per_image", None)
+        per_image = K == 1 if per_image is None else bool(per_image)
+        lw = getattr(args, "lovasz_weight", 1.0)
+        if K > 1:
+            seg = dict(ignore_index=args.ignore_index, classes=getattr(args, "lovasz_classes", "present"),
+                       per_image=per_image)
+            return LovaszSoftmaxLoss(**seg) if kind == "lovasz" else CELovaszLoss(lovasz_weight=lw, **seg)
+        return LovaszHingeLoss(per_image) if kind == "lovasz" else BCELovaszLoss(per_image, lovasz_weight=lw)
     if kind not in ("dice", "ce+dice"):
-        raise ValueError(f"--loss must be ce, dice or ce+dice, got {kind!r}")
+        raise ValueError(f"--loss must be ce, dice, ce+dice, lovasz or ce+lovasz, got {kind!r}")
     smooth = getattr(args, "dice_smooth", 1.0)
     if kind == "dice":
         if K > 1:

@@ -1,5 +1,5 @@
 // Torch binding of the losses and evaluation counts (kernels/loss.hip, cls_ce.hip, pixel_ce.hip, seg_dice.hip,
-// ohem.hip).
+// ohem.hip, lovasz.hip).
 // softmax_ce_*, bce_*, argmax_correct and dice take their shapes from the caller (NativeBackend) unchecked.
 #include <algorithm>
 #include <cmath>
@@ -338,6 +338,107 @@ void ohem_bce_bwd(const at::Tensor& logits, const at::Tensor& target, int64_t M,
                            optr<float>(go), ptr<float>(den), ptr<float>(dlogits), cur_stream()),
         "ohem_bce_bwd");
 }
+// Lovasz-Softmax / Lovasz hinge (lovasz.hip).  S segments of L pixels; the workspace (keys and payloads ping-pong,
+// histograms, partials) comes from the caching allocator per call.  g fp32 [S * L], coef fp32 [S], stats int32 [2 + S].
+void lovasz_weight_check(double a, double b, const char* fn) {
+  if (!std::isfinite(a) || !std::isfinite(b) || a < 0 || b < 0)
+    fail(fn, "the two loss weights must be finite and >= 0");
+}
+at::Tensor lovasz_ws(const char* fn, int64_t S, int64_t L, int64_t M, const at::Tensor& like) {
+  if (L >= 2147483648LL) fail(fn, "a segment's pixels are indexed in 31 bits: L < 2^31");
+  const int64_t words = dlmpi_lovasz_ws_words(S, L, M);
+  if (words < 0) fail(fn, "1 <= segments <= 65535 and 1 <= pixels per segment < 2^31");
+  return at::empty({words}, like.options().dtype(at::kInt));
+}
+void lovasz_out_check(const char* fn, int64_t S, int64_t L, const at::Tensor& g, const at::Tensor& coef,
+                      const at::Tensor* stats) {
+  dense(g, at::kFloat, S * L, fn, "g");
+  dense(coef, at::kFloat, S, fn, "coef");
+  if (stats) dense(*stats, at::kInt, 2 + S, fn, "stats");
+}
+void lovasz_rank(const at::Tensor& err, const at::Tensor& fg, const at::Tensor& valid, bool hinge, at::Tensor g,
+                 at::Tensor perm, at::Tensor seg_loss) {
+  if (err.dim() != 2 || err.numel() < 1) fail("lovasz_rank", "err must be [S, L] with S, L >= 1");
+  const int64_t S = err.size(0), L = err.size(1);
+  dense(err, at::kFloat, S * L, "lovasz_rank", "err");
+  dense(fg, at::kByte, S * L, "lovasz_rank", "fg");
+  dense(valid, at::kByte, S * L, "lovasz_rank", "valid");
+  dense(g, at::kFloat, S * L, "lovasz_rank", "g");
+  dense(perm, at::kInt, S * L, "lovasz_rank", "perm");
+  dense(seg_loss, at::kFloat, S, "lovasz_rank", "seg_loss");
+  at::Tensor ws = lovasz_ws("lovasz_rank", S, L, 1, err);
+  check(dlmpi_lovasz_rank(ptr<float>(err), ptr<uint8_t>(fg), ptr<uint8_t>(valid), S, L, hinge ? 1 : 0,
+                          ptr<uint32_t>(ws), ptr<float>(g), ptr<int32_t>(perm), ptr<float>(seg_loss), cur_stream()),
+        "lovasz_rank");
+}
+void lovasz_softmax_fwd(const at::Tensor& logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                        const at::Tensor& labels, int64_t ignore_index, bool per_image, bool classes_all,
+                        double ce_weight, double lovasz_weight, at::Tensor lse, at::Tensor g, at::Tensor coef,
+                        at::Tensor stats, at::Tensor loss, at::Tensor den) {
+  const char* fn = "lovasz_softmax_fwd";
+  pix_fwd_check(fn, logits, sn, sk, sp, N, K, HW, labels, c10::nullopt, lse, den, nullptr, &loss);
+  lovasz_weight_check(ce_weight, lovasz_weight, fn);
+  const int64_t M = (int64_t)N * HW, S = per_image ? (int64_t)N * K : K, L = per_image ? HW : M;
+  at::Tensor ws = lovasz_ws(fn, S, L, M, logits);
+  lovasz_out_check(fn, S, L, g, coef, &stats);
+  check(dlmpi_lovasz_softmax_fwd(ptr<float>(logits), sn, sk, sp, N, K, HW, ptr<int64_t>(labels), ignore_index,
+                                 per_image ? 1 : 0, classes_all ? 1 : 0, (float)ce_weight, (float)lovasz_weight,
+                                 ptr<float>(lse), ptr<uint32_t>(ws), ptr<float>(g), ptr<float>(coef),
+                                 ptr<int32_t>(stats), ptr<float>(loss), ptr<float>(den), cur_stream()),
+        fn);
+}
+void lovasz_softmax_bwd(const at::Tensor& logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                        const at::Tensor& labels, int64_t ignore_index, bool per_image, const at::Tensor& lse,
+                        const at::Tensor& g, const at::Tensor& coef, const at::Tensor& den,
+                        const c10::optional<at::Tensor>& go, double ce_weight, double lovasz_weight,
+                        at::Tensor dlogits) {
+  const char* fn = "lovasz_softmax_bwd";
+  pix_bwd_check(fn, logits, sn, sk, sp, N, K, HW, labels, c10::nullopt, lse, den, nullptr, dlogits, go);
+  lovasz_weight_check(ce_weight, lovasz_weight, fn);
+  const int64_t M = (int64_t)N * HW, S = per_image ? (int64_t)N * K : K, L = per_image ? HW : M;
+  lovasz_out_check(fn, S, L, g, coef, nullptr);
+  check(dlmpi_lovasz_softmax_bwd(ptr<float>(logits), sn, sk, sp, N, K, HW, ptr<int64_t>(labels), ignore_index,
+                                 per_image ? 1 : 0, ptr<float>(lse), ptr<float>(g), ptr<float>(coef), ptr<float>(den),
+                                 optr<float>(go), (float)ce_weight, (float)lovasz_weight, ptr<float>(dlogits),
+                                 cur_stream()),
+        fn);
+}
+// logits, target: contiguous fp32 [N][HW]
+void lovasz_hinge_fwd(const at::Tensor& logits, const at::Tensor& target, int N, int64_t HW, bool per_image,
+                      double bce_weight, double lovasz_weight, at::Tensor g, at::Tensor coef, at::Tensor stats,
+                      at::Tensor loss, at::Tensor den) {
+  const char* fn = "lovasz_hinge_fwd";
+  if (N < 1 || HW < 1) fail(fn, "N, HW >= 1");
+  const int64_t M = (int64_t)N * HW, S = per_image ? N : 1, L = per_image ? HW : M;
+  dense(logits, at::kFloat, M, fn, "logits");
+  dense(target, at::kFloat, M, fn, "target");
+  lovasz_weight_check(bce_weight, lovasz_weight, fn);
+  at::Tensor ws = lovasz_ws(fn, S, L, M, logits);
+  lovasz_out_check(fn, S, L, g, coef, &stats);
+  dense(loss, at::kFloat, 1, fn, "loss");
+  dense(den, at::kFloat, 1, fn, "den");
+  check(dlmpi_lovasz_hinge_fwd(ptr<float>(logits), ptr<float>(target), N, HW, per_image ? 1 : 0, (float)bce_weight,
+                               (float)lovasz_weight, ptr<uint32_t>(ws), ptr<float>(g), ptr<float>(coef),
+                               ptr<int32_t>(stats), ptr<float>(loss), ptr<float>(den), cur_stream()),
+        fn);
+}
+void lovasz_hinge_bwd(const at::Tensor& logits, const at::Tensor& target, int N, int64_t HW, bool per_image,
+                      const at::Tensor& g, const at::Tensor& coef, const c10::optional<at::Tensor>& go,
+                      double bce_weight, double lovasz_weight, at::Tensor dlogits) {
+  const char* fn = "lovasz_hinge_bwd";
+  if (N < 1 || HW < 1) fail(fn, "N, HW >= 1");
+  const int64_t M = (int64_t)N * HW, S = per_image ? N : 1, L = per_image ? HW : M;
+  dense(logits, at::kFloat, M, fn, "logits");
+  dense(target, at::kFloat, M, fn, "target");
+  dense(dlogits, at::kFloat, M, fn, "dlogits");
+  lovasz_weight_check(bce_weight, lovasz_weight, fn);
+  lovasz_out_check(fn, S, L, g, coef, nullptr);
+  dense(go, at::kFloat, 1, fn, "go");
+  check(dlmpi_lovasz_hinge_bwd(ptr<float>(logits), ptr<float>(target), N, HW, per_image ? 1 : 0, ptr<float>(g),
+                               ptr<float>(coef), optr<float>(go), (float)bce_weight, (float)lovasz_weight,
+                               ptr<float>(dlogits), cur_stream()),
+        fn);
+}
 }  // namespace
 
 void register_loss(pybind11::module& m) {
@@ -370,6 +471,12 @@ void register_loss(pybind11::module& m) {
   m.def("ohem_bce_fwd", &ohem_bce_fwd);
   m.def("ohem_bce_bwd", &ohem_bce_bwd);
   m.def("set_ohem_aggregate", [](int on) { dlmpi_set_ohem_aggregate(on); });
+  m.def("lovasz_tile", []() { return dlmpi_lovasz_tile(); });
+  m.def("lovasz_rank", &lovasz_rank);
+  m.def("lovasz_softmax_fwd", &lovasz_softmax_fwd);
+  m.def("lovasz_softmax_bwd", &lovasz_softmax_bwd);
+  m.def("lovasz_hinge_fwd", &lovasz_hinge_fwd);
+  m.def("lovasz_hinge_bwd", &lovasz_hinge_bwd);
 }
 
 }  // namespace dlmpi_ext

@@ -480,6 +480,32 @@ hipError_t dlmpi_ohem_bce_fwd(const float* logits, const float* target, int64_t 
                               uint32_t* state, float* loss, float* den, hipStream_t s);
 hipError_t dlmpi_ohem_bce_bwd(const float* logits, const float* target, int64_t M, const float* nll, const float* cut,
                               const float* go, const float* den, float* dlogits, hipStream_t s);
+// Lovasz-Softmax / Lovasz hinge (lovasz.hip; the definition is at the top of that file).  S segments of L pixels:
+// S = K, L = N * HW, or with per_image S = N * K, L = HW (hinge: K = 1); S <= 65535, L < 2^31.  ws:
+// dlmpi_lovasz_ws_words(S, L, N * HW) uint32 (-1: a refused shape), nothing in it needs zeroing; g fp32 [S][L], coef
+// fp32 [S], stats int32 [2 + S] = {n_valid, counted segments, fg count per segment}, den = n_valid.
+// loss = ce_weight * (plain unweighted CE / BCE) + lovasz_weight * Lovasz.  No host read, no float atomics.
+int dlmpi_lovasz_tile();   // items per sort tile
+int64_t dlmpi_lovasz_ws_words(int64_t S, int64_t L, int64_t M);
+// the sort and the Jaccard gradient alone on a caller's errors: perm [S][L] = the pixel at each rank (valid ones
+// first), g at the pixel's own index (0 where not valid), seg_loss [S] = sum e g (hinge: sum max(e, 0) g)
+hipError_t dlmpi_lovasz_rank(const float* err, const uint8_t* fg, const uint8_t* valid, int64_t S, int64_t L,
+                             int hinge, uint32_t* ws, float* g, int32_t* perm, float* seg_loss, hipStream_t s);
+hipError_t dlmpi_lovasz_softmax_fwd(const float* logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                                    const int64_t* labels, int64_t ignore_index, int per_image, int classes_all,
+                                    float ce_weight, float lovasz_weight, float* lse, uint32_t* ws, float* g,
+                                    float* coef, int32_t* stats, float* loss, float* den, hipStream_t s);
+hipError_t dlmpi_lovasz_softmax_bwd(const float* logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                                    const int64_t* labels, int64_t ignore_index, int per_image, const float* lse,
+                                    const float* g, const float* coef, const float* den, const float* go,
+                                    float ce_weight, float lovasz_weight, float* dlogits, hipStream_t s);
+// hinge form: contiguous logits / float targets [N][HW], fg = [t > 0.5]
+hipError_t dlmpi_lovasz_hinge_fwd(const float* logits, const float* target, int N, int64_t HW, int per_image,
+                                  float bce_weight, float lovasz_weight, uint32_t* ws, float* g, float* coef,
+                                  int32_t* stats, float* loss, float* den, hipStream_t s);
+hipError_t dlmpi_lovasz_hinge_bwd(const float* logits, const float* target, int N, int64_t HW, int per_image,
+                                  const float* g, const float* coef, const float* go, float bce_weight,
+                                  float lovasz_weight, float* dlogits, hipStream_t s);
 
 // eval
 hipError_t dlmpi_argmax_correct(const float* logits, int ldl, const int64_t* labels, int N, int K, int* correct,

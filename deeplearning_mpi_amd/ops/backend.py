@@ -600,6 +600,71 @@ class NativeBackend:
         self.C.ohem_bce_bwd(logits, target, logits.numel(), nll, cut, go, den, d)
         return d
 
+    # Lovasz-Softmax / Lovasz hinge (lovasz.hip): S segments of L pixels, S = K and L = N H W, or with per_image
+    # S = N K and L = H W (hinge: K = 1).  g [S * L] is the Jaccard gradient at each pixel's own index, coef [S] a
+    # counted segment's share of the mean; stats are views of one device vector that nothing here reads.
+    @property
+    def lovasz_tile(self):
+        """Items per tile of the radix sort (the sizes around it are the edge cases of its tests)."""
+        return self.C.lovasz_tile()
+
+    @staticmethod
+    def _lovasz_stats(stats):
+        return {"n_valid": stats[0:1], "n_classes": stats[1:2], "fg_counts": stats[2:]}
+
+    def _lovasz_out(self, like, S, L):   # g [S * L], coef [S], stats int32 [2 + S], loss (scalar), den [1]
+        f32 = dict(dtype=torch.float32, device=like.device)
+        return (torch.empty(S * L, **f32), torch.empty(S, **f32),
+                torch.empty(2 + S, dtype=torch.int32, device=like.device), torch.empty((), **f32),
+                torch.empty(1, **f32))
+
+    def lovasz_sort(self, err, fg, valid, hinge=False):
+        """The segmented sort and the Jaccard gradient alone: err fp32 [S, L], fg / valid bool [S, L] -> (perm int64
+        [S, L]: the pixel at each rank, valid ones first, g fp32 [S, L] at the pixel's own index, seg_loss [S])."""
+        S, L = err.shape
+        g = torch.empty(S, L, dtype=torch.float32, device=err.device)
+        perm = torch.empty(S, L, dtype=torch.int32, device=err.device)
+        seg_loss = torch.empty(S, dtype=torch.float32, device=err.device)
+        self.C.lovasz_rank(err.contiguous(), fg.to(torch.uint8).contiguous(), valid.to(torch.uint8).contiguous(),
+                           bool(hinge), g, perm, seg_loss)
+        return perm.long(), g, seg_loss
+
+    def lovasz_softmax_fwd(self, logits, labels, ignore_index=-100, classes="present", per_image=False,
+                           ce_weight=0.0, lovasz_weight=1.0):
+        """-> (ce_weight * CE + lovasz_weight * Lovasz-Softmax, lse [N*H*W], g, coef, den = n_valid, stats)."""
+        N, K, H, W = logits.shape
+        lse = torch.empty(N * H * W, dtype=torch.float32, device=logits.device)
+        S, L = (N * K, H * W) if per_image else (K, N * H * W)
+        g, coef, stats, loss, den = self._lovasz_out(logits, S, L)
+        self.C.lovasz_softmax_fwd(logits, *pixel_strides(logits), N, K, H * W, labels, int(ignore_index),
+                                  bool(per_image), classes == "all", float(ce_weight), float(lovasz_weight), lse, g,
+                                  coef, stats, loss, den)
+        return loss, lse, g, coef, den, self._lovasz_stats(stats)
+
+    def lovasz_softmax_bwd(self, logits, labels, lse, g, coef, den, go, ignore_index=-100, per_image=False,
+                           ce_weight=0.0, lovasz_weight=1.0):
+        N, K, H, W = logits.shape
+        d = self._pixel_dlogits(logits)
+        self.C.lovasz_softmax_bwd(logits, *pixel_strides(logits), N, K, H * W, labels, int(ignore_index),
+                                  bool(per_image), lse, g, coef, den, go, float(ce_weight), float(lovasz_weight), d)
+        return d
+
+    def lovasz_hinge_fwd(self, logits, target, per_image=True, bce_weight=0.0, lovasz_weight=1.0):
+        """logits, target fp32 contiguous [N, ...] -> (bce_weight * BCE + lovasz_weight * Lovasz hinge, g, coef,
+        stats)."""
+        N, HW = logits.shape[0], logits[0].numel()
+        S, L = (N, HW) if per_image else (1, N * HW)
+        g, coef, stats, loss, den = self._lovasz_out(logits, S, L)
+        self.C.lovasz_hinge_fwd(logits, target, N, HW, bool(per_image), float(bce_weight), float(lovasz_weight), g,
+                                coef, stats, loss, den)
+        return loss, g, coef, self._lovasz_stats(stats)
+
+    def lovasz_hinge_bwd(self, logits, target, g, coef, go, per_image=True, bce_weight=0.0, lovasz_weight=1.0):
+        d = torch.empty_like(logits, memory_format=torch.contiguous_format)
+        self.C.lovasz_hinge_bwd(logits, target, logits.shape[0], logits[0].numel(), bool(per_image), g, coef, go,
+                                float(bce_weight), float(lovasz_weight), d)
+        return d
+
     def bce_fwd(self, logits, target):
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
         self.C.bce_fwd(logits, 1, target, logits.numel(), loss)
@@ -1202,6 +1267,104 @@ class RefBackend:
         sel = ((nll >= cut) | torch.isnan(nll)).view(logits.shape)
         d = (torch.sigmoid(logits.to(self.dt)) - target) * (go if go is not None else 1.0) / den
         return torch.where(sel, d, torch.zeros((), dtype=self.dt, device=d.device))
+
+    # Lovasz-Softmax / Lovasz hinge: the definition of csrc/kernels/lovasz.hip with torch's stable sort
+    lovasz_tile = 2048   # the native sort's tile, so that tests take the same sizes on either backend
+
+    def lovasz_sort(self, err, fg, valid, hinge=False):
+        """err [S, L], fg / valid bool [S, L] -> (perm int64 [S, L], g [S, L] at the pixel's own index, seg_loss
+        [S]): valid pixels by err descending (stable; a NaN first), the invalid ones after them."""
+        L = err.shape[1]
+        perm = torch.sort(err, dim=1, descending=True, stable=True).indices
+        last = (~valid).gather(1, perm).to(torch.uint8)
+        perm = perm.gather(1, torch.sort(last, dim=1, stable=True).indices)
+        vs, fgs = valid.gather(1, perm), (fg & valid).gather(1, perm)
+        G = fgs.sum(1, keepdim=True)
+        Fb = fgs.cumsum(1) - fgs.long()                        # fg pixels strictly before
+        U = G + torch.arange(L, device=err.device).unsqueeze(0) - Fb
+        Ud = U.double()
+        gd = torch.where(fgs, 1 / Ud.clamp_min(1), torch.where(U == 0, torch.ones_like(Ud),
+                                                               (G - Fb).double() / (Ud * (Ud + 1)).clamp_min(1)))
+        gs = torch.where(vs, gd, torch.zeros_like(gd)).to(err.dtype)
+        es = err.gather(1, perm)
+        if hinge:
+            es = es.clamp_min(0)   # (keeps a NaN)
+        seg_loss = torch.where(vs, es * gs, torch.zeros_like(es)).sum(1)
+        return perm, torch.zeros_like(gs).scatter(1, perm, gs), seg_loss
+
+    def _lovasz_mean(self, seg_loss, G, Ns, K, all_classes):
+        """-> (the mean over Ns samples of the mean over each one's counted segments, coef [S], stats' counts)."""
+        counted = (torch.ones_like(G, dtype=torch.bool) if all_classes else G > 0).view(Ns, K)
+        cnt = counted.sum(1, keepdim=True)
+        coef = torch.where(counted, 1 / (Ns * cnt.clamp_min(1)).to(self.dt), torch.zeros((), dtype=self.dt)).reshape(-1)
+        return (coef * seg_loss).sum(), coef, cnt.sum().to(torch.int32).reshape(1)
+
+    def lovasz_softmax_fwd(self, logits, labels, ignore_index=-100, classes="present", per_image=False,
+                           ce_weight=0.0, lovasz_weight=1.0):
+        x = logits.to(self.dt)
+        N, K, H, W = x.shape
+        keep = self._pix_keep(labels, K, ignore_index).unsqueeze(1)
+        lse = torch.logsumexp(x, 1)
+        fg = (labels.unsqueeze(1) == torch.arange(K, device=x.device).view(1, K, 1, 1)) & keep
+        e = (fg.to(self.dt) - torch.exp(x - lse.unsqueeze(1))).abs()
+
+        def seg(t):
+            return t.reshape(N * K, H * W) if per_image else t.permute(1, 0, 2, 3).reshape(K, N * H * W)
+
+        _, g, seg_loss = self.lovasz_sort(seg(e), seg(fg), seg(keep.expand(N, K, H, W)))
+        G = seg(fg).sum(1)
+        lov, coef, ncls = self._lovasz_mean(seg_loss, G, N if per_image else 1, K, classes == "all")
+        loss = lovasz_weight * lov
+        if ce_weight != 0:
+            loss = loss + ce_weight * self.pixel_ce_fwd(logits, labels, None, ignore_index)[0]
+        nv = keep.sum()
+        stats = {"n_valid": nv.to(torch.int32).reshape(1), "n_classes": ncls, "fg_counts": G.to(torch.int32)}
+        return loss, lse.reshape(-1), g.reshape(-1), coef, nv.to(self.dt).reshape(1), stats
+
+    def lovasz_softmax_bwd(self, logits, labels, lse, g, coef, den, go, ignore_index=-100, per_image=False,
+                           ce_weight=0.0, lovasz_weight=1.0):
+        x = logits.to(self.dt)
+        N, K, H, W = x.shape
+        keep = self._pix_keep(labels, K, ignore_index).unsqueeze(1)
+        oh = F.one_hot(labels.clamp(0, K - 1), K).permute(0, 3, 1, 2).to(self.dt)
+        p = torch.exp(x - lse.view(N, 1, H, W))
+        gk = g.view(N, K, H, W) if per_image else g.view(K, N, H, W).permute(1, 0, 2, 3)
+        ck = coef.view(N, K, 1, 1) if per_image else coef.view(1, K, 1, 1)
+        go = go if go is not None else 1.0
+        a = (1 - 2 * oh) * gk * ck * (lovasz_weight * go)
+        d = p * (a - (a * p).sum(1, keepdim=True))
+        if ce_weight != 0:
+            d = d + (p - oh) * (ce_weight * go / den)
+        out = torch.empty_like(logits, dtype=self.dt)
+        out.copy_(torch.where(keep, d, torch.zeros((), dtype=self.dt, device=x.device)))
+        return out
+
+    def lovasz_hinge_fwd(self, logits, target, per_image=True, bce_weight=0.0, lovasz_weight=1.0):
+        N = logits.shape[0]
+        rows = N if per_image else 1
+        x, t = logits.to(self.dt).reshape(rows, -1), target.to(self.dt).reshape(rows, -1)
+        fg = t > 0.5
+        e = 1 - x * (2 * fg.to(self.dt) - 1)
+        _, g, seg_loss = self.lovasz_sort(e, fg, torch.ones_like(fg), hinge=True)
+        G = fg.sum(1)
+        lov, coef, ncls = self._lovasz_mean(seg_loss, G, rows, 1, True)
+        loss = lovasz_weight * lov
+        if bce_weight != 0:
+            loss = loss + bce_weight * F.binary_cross_entropy_with_logits(x, t)
+        stats = {"n_valid": torch.tensor([x.numel()], dtype=torch.int32, device=x.device), "n_classes": ncls,
+                 "fg_counts": G.to(torch.int32)}
+        return loss, g.reshape(-1), coef, stats
+
+    def lovasz_hinge_bwd(self, logits, target, g, coef, go, per_image=True, bce_weight=0.0, lovasz_weight=1.0):
+        rows = logits.shape[0] if per_image else 1
+        x, t = logits.to(self.dt).reshape(rows, -1), target.to(self.dt).reshape(rows, -1)
+        sgn = 2 * (t > 0.5).to(self.dt) - 1
+        go = go if go is not None else 1.0
+        d = torch.where(1 - x * sgn > 0, -sgn * g.view(rows, -1) * coef.view(rows, 1) * (lovasz_weight * go),
+                        torch.zeros((), dtype=self.dt, device=x.device))
+        if bce_weight != 0:
+            d = d + (torch.sigmoid(x) - t) * (bce_weight * go / x.numel())
+        return d.view(logits.shape)
 
     def bce_fwd(self, logits, target):
         return F.binary_cross_entropy_with_logits(logits.to(self.dt), target.to(self.dt))

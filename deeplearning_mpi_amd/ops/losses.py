@@ -288,6 +288,177 @@ def ohem_bce_with_logits(logits, target, keep_ratio=0.25, min_kept=1, thresh=Non
     return _ohem_bce(logits, target, keep_ratio, min_kept, thresh)[0]
 
 
+_LOVASZ_STATS = ("n_valid", "n_classes", "fg_counts")
+
+
+class _LovaszSoftmax(torch.autograd.Function):
+    """ce_weight * pixel-wise cross-entropy + lovasz_weight * Lovasz-Softmax (csrc/kernels/lovasz.hip): logits read
+    in place, the gradient in their strides; returns the loss and the three device statistics."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index, classes, per_image, ce_weight, lovasz_weight):
+        be, x, labels, _ = _pixel_inputs(logits, labels, None)
+        loss, lse, g, coef, den, st = be.lovasz_softmax_fwd(x, labels, ignore_index, classes, per_image, ce_weight,
+                                                            lovasz_weight)
+        ctx.save_for_backward(x, labels, lse, g, coef, den)
+        ctx.args, ctx.in_dtype = (ignore_index, per_image, ce_weight, lovasz_weight), logits.dtype
+        stats = tuple(st[n] for n in _LOVASZ_STATS)
+        ctx.mark_non_differentiable(*stats)
+        return (loss,) + stats
+
+    @staticmethod
+    def backward(ctx, go, *_):
+        x, labels, lse, g, coef, den = ctx.saved_tensors
+        be = _be(x.device, x.dtype)
+        d = be.lovasz_softmax_bwd(x, labels, lse, g, coef, den, go.reshape(1).to(be.dt).contiguous(), *ctx.args)
+        return (d.to(ctx.in_dtype),) + (None,) * 6
+
+
+class _LovaszHinge(torch.autograd.Function):
+    """bce_weight * BCE-with-logits + lovasz_weight * Lovasz hinge: contiguous logits and float targets [N, ...]."""
+
+    @staticmethod
+    def forward(ctx, logits, target, per_image, bce_weight, lovasz_weight):
+        be = _be(logits.device, logits.dtype)
+        x = logits.contiguous().to(be.dt)
+        target = target.contiguous().to(be.dt)
+        loss, g, coef, st = be.lovasz_hinge_fwd(x, target, per_image, bce_weight, lovasz_weight)
+        ctx.save_for_backward(x, target, g, coef)
+        ctx.args, ctx.in_dtype = (per_image, bce_weight, lovasz_weight), logits.dtype
+        stats = tuple(st[n] for n in _LOVASZ_STATS)
+        ctx.mark_non_differentiable(*stats)
+        return (loss,) + stats
+
+    @staticmethod
+    def backward(ctx, go, *_):
+        x, target, g, coef = ctx.saved_tensors
+        be = _be(x.device, x.dtype)
+        d = be.lovasz_hinge_bwd(x, target, g, coef, go.reshape(1).to(be.dt).contiguous(), *ctx.args)
+        return d.view(x.shape).to(ctx.in_dtype), None, None, None, None
+
+
+def _check_lovasz_args(w0, w1, names, classes="present"):
+    for v, n in ((w0, names[0]), (w1, names[1])):
+        if not math.isfinite(v) or v < 0:
+            raise ValueError(f"{n} must be finite and >= 0, got {v}")
+    if w0 == 0 and w1 == 0:
+        raise ValueError(f"{names[0]} and {names[1]} must not both be 0")
+    if classes not in ("present", "all"):
+        raise ValueError(f"classes must be 'present' or 'all', got {classes!r}")
+
+
+def _lovasz_softmax(logits, labels, ignore_index, classes, per_image, ce_weight, lovasz_weight):
+    ce_weight, lovasz_weight = float(ce_weight), float(lovasz_weight)
+    _check_lovasz_args(ce_weight, lovasz_weight, ("ce_weight", "lovasz_weight"), classes)
+    if logits.dim() != 4:
+        raise ValueError(f"the Lovasz-Softmax loss takes [N, K, H, W] logits, got {tuple(logits.shape)}")
+    _check_pixel_args(logits, labels)
+    if lovasz_weight == 0:
+        loss = _PixelCE.apply(logits, labels, None, int(ignore_index))
+        return (loss if ce_weight == 1 else loss * ce_weight), None
+    out = _LovaszSoftmax.apply(logits, labels, int(ignore_index), classes, bool(per_image), ce_weight, lovasz_weight)
+    return out[0], dict(zip(_LOVASZ_STATS, out[1:]))
+
+
+def _lovasz_hinge(logits, target, per_image, bce_weight, lovasz_weight):
+    bce_weight, lovasz_weight = float(bce_weight), float(lovasz_weight)
+    _check_lovasz_args(bce_weight, lovasz_weight, ("bce_weight", "lovasz_weight"))
+    if logits.dim() == target.dim() + 1 and logits.shape[1] == 1:
+        logits = logits.squeeze(1)
+    if target.dim() < 2 or logits.shape != target.shape or not target.is_floating_point():
+        raise ValueError(f"the Lovasz hinge loss takes logits [N, H, W] or [N, 1, H, W] and a float target [N, H, W], "
+                         f"got {tuple(logits.shape)} and {target.dtype} {tuple(target.shape)}")
+    if lovasz_weight == 0:
+        loss = _BCE.apply(logits, target)
+        return (loss if bce_weight == 1 else loss * bce_weight), None
+    out = _LovaszHinge.apply(logits, target, bool(per_image), bce_weight, lovasz_weight)
+    return out[0], dict(zip(_LOVASZ_STATS, out[1:]))
+
+
+def lovasz_softmax(logits, labels, ignore_index=-100, classes="present", per_image=False):
+    """The Lovasz-Softmax loss (Berman et al., CVPR 2018), the Lovasz extension of the Jaccard loss, for
+    [N, K, H, W] logits and int64 [N, H, W] labels.  A segment is the set of pixels ranked together: one per class
+    over the batch, or with ``per_image`` one per (sample, class).  A pixel is valid as in :func:`cross_entropy`
+    (neither ``ignore_index`` nor outside [0, K)); invalid pixels get no rank, no count and an exact zero gradient.
+    With p the softmax, fg = [y = c] and e = |fg - p_c|, a segment's valid pixels are ranked by e descending, equal
+    e by ascending pixel index (n, h, w) -- a stable sort; -0 counts as +0, a NaN ranks first.  With G the segment's
+    fg count, i a pixel's 0-based rank, F the fg pixels strictly before it, R = G - F and U = G + i - F, the Jaccard
+    gradient is g = 1 / U (fg), R / (U (U + 1)) (bg), 1 where U = 0 (an absent class) -- J_i - J_{i-1} of the paper,
+    formed in fp64 from the integers -- and the segment's loss is sum e g.  ``classes="present"`` averages the
+    segments with G > 0, ``"all"`` every class; ``per_image`` averages over the samples each one's mean over its
+    counted classes (0 for a sample without one).  Nothing to count: loss 0, zero gradient.  The gradient goes
+    through e with g held constant.  On the GPU the ranking is a segmented stable radix sort
+    (csrc/kernels/lovasz.hip): no host synchronisation, the same bits on every run."""
+    return _lovasz_softmax(logits, labels, ignore_index, classes, per_image, 0.0, 1.0)[0]
+
+
+def lovasz_hinge(logits, target, per_image=True):
+    """The binary Lovasz hinge loss for logits [N, H, W] or [N, 1, H, W] and a float target [N, H, W]: fg =
+    [t > 0.5], e = 1 - x (2 fg - 1), every pixel valid, one class; ranking and g as :func:`lovasz_softmax`, the
+    segment's loss is sum max(e, 0) g and dx = -(2 fg - 1) g [e > 0].  ``per_image`` (the paper's default) ranks
+    each sample on its own and averages the samples."""
+    return _lovasz_hinge(logits, target, per_image, 0.0, 1.0)[0]
+
+
+def ce_lovasz_loss(logits, labels, ignore_index=-100, classes="present", per_image=False, ce_weight=1.0,
+                   lovasz_weight=1.0):
+    """``ce_weight * CE + lovasz_weight * Lovasz-Softmax`` with CE the plain unweighted :func:`cross_entropy` over
+    the valid pixels.  On the GPU the CE sum rides in the error pass and its gradient in the one backward pass;
+    ``lovasz_weight=0`` is :func:`cross_entropy` itself (the plain kernels), ``ce_weight=0`` the Lovasz term alone."""
+    return _lovasz_softmax(logits, labels, ignore_index, classes, per_image, ce_weight, lovasz_weight)[0]
+
+
+def bce_lovasz_loss(logits, target, per_image=True, bce_weight=1.0, lovasz_weight=1.0):
+    """``bce_weight * BCE + lovasz_weight * Lovasz hinge``; ``lovasz_weight=0`` is :func:`bce_with_logits` itself."""
+    return _lovasz_hinge(logits, target, per_image, bce_weight, lovasz_weight)[0]
+
+
+class CELovaszLoss(nn.Module):
+    """:func:`ce_lovasz_loss`; ``last_stats`` holds the latest forward's device tensors ``n_valid``, ``n_classes``
+    (counted segments) and ``fg_counts`` (int32), which the library itself never reads (None at
+    ``lovasz_weight=0``)."""
+
+    def __init__(self, ignore_index=-100, classes="present", per_image=False, ce_weight=1.0, lovasz_weight=1.0):
+        super().__init__()
+        _check_lovasz_args(float(ce_weight), float(lovasz_weight), ("ce_weight", "lovasz_weight"), classes)
+        self.ignore_index, self.classes, self.per_image = ignore_index, classes, per_image
+        self.ce_weight, self.lovasz_weight = ce_weight, lovasz_weight
+        self.last_stats = None
+
+    def forward(self, logits, labels):
+        loss, self.last_stats = _lovasz_softmax(logits, labels, self.ignore_index, self.classes, self.per_image,
+                                                self.ce_weight, self.lovasz_weight)
+        return loss
+
+
+class LovaszSoftmaxLoss(CELovaszLoss):
+    """:func:`lovasz_softmax`; ``last_stats`` as :class:`CELovaszLoss`."""
+
+    def __init__(self, ignore_index=-100, classes="present", per_image=False):
+        super().__init__(ignore_index, classes, per_image, 0.0, 1.0)
+
+
+class BCELovaszLoss(nn.Module):
+    """:func:`bce_lovasz_loss`; ``last_stats`` as :class:`CELovaszLoss`."""
+
+    def __init__(self, per_image=True, bce_weight=1.0, lovasz_weight=1.0):
+        super().__init__()
+        _check_lovasz_args(float(bce_weight), float(lovasz_weight), ("bce_weight", "lovasz_weight"))
+        self.per_image, self.bce_weight, self.lovasz_weight = per_image, bce_weight, lovasz_weight
+        self.last_stats = None
+
+    def forward(self, logits, target):
+        loss, self.last_stats = _lovasz_hinge(logits, target, self.per_image, self.bce_weight, self.lovasz_weight)
+        return loss
+
+
+class LovaszHingeLoss(BCELovaszLoss):
+    """:func:`lovasz_hinge`; ``last_stats`` as :class:`CELovaszLoss`."""
+
+    def __init__(self, per_image=True):
+        super().__init__(per_image, 0.0, 1.0)
+
+
 class _PixelCEDice(torch.autograd.Function):
     """ce_weight * pixel-wise cross-entropy + dice_weight * soft Dice in the passes of _PixelCE: one fused
     forward, one finish, one fused backward; logits read in place, gradient in their strides."""
