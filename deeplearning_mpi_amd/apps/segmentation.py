@@ -30,10 +30,16 @@ the device (csrc/kernels/ohem.hip), so the step stays capturable.
 (ops.lovasz_softmax / ce_lovasz_loss for K > 1, ops.lovasz_hinge / bce_lovasz_loss for --num_classes 1;
 --lovasz_weight, --lovasz_per_image, --lovasz_classes): the pixels of every class are ranked by a segmented radix
 sort on the device (csrc/kernels/lovasz.hip), so the step stays capturable.
+--loss boundary / ce+boundary trains on the boundary loss of Kervadec et al., alone or added to the plain CE / BCE
+(ops.boundary_loss / ce_boundary_loss, the sigmoid form for --num_classes 1): the signed distance map of each step's
+masks is an exact Euclidean distance transform on the device (csrc/kernels/edt.hip), so the step stays capturable.
+--boundary_weight A, --boundary_ramp D: the term's weight A + D * epoch lives in a device scalar written at each epoch
+start, outside the captured step; --boundary_background 0 leaves class 0 out.
 """
 from __future__ import annotations
 
 import argparse
+import math
 import os
 import sys
 import random
@@ -49,9 +55,9 @@ from .. import parallel
 from ..data import (CarvanaDataset, DeviceBatches, DeviceCachedDataset, DeviceSegDataset, DistributedSampler,
                     SegAugConfig, SyntheticMasks)
 from ..models import UNet
-from ..ops import (BCEDiceLoss, BCELovaszLoss, BCEWithLogitsLoss, CEDiceLoss, CELovaszLoss, CrossEntropyLoss, DiceLoss,
-                   LovaszHingeLoss, LovaszSoftmaxLoss, OHEMBCEWithLogitsLoss, OHEMCrossEntropyLoss, backward,
-                   dice_multiclass, dice_per_sample)
+from ..ops import (BCEBoundaryLoss, BCEDiceLoss, BCELovaszLoss, BCEWithLogitsLoss, BoundaryLoss, CEBoundaryLoss,
+                   CEDiceLoss, CELovaszLoss, CrossEntropyLoss, DiceLoss, LovaszHingeLoss, LovaszSoftmaxLoss,
+                   OHEMBCEWithLogitsLoss, OHEMCrossEntropyLoss, backward, dice_multiclass, dice_per_sample)
 from ..optim import LAMB, Adam, clip_grad_norm_
 from ..utils.graphs import CapturedStep
 from ..utils.checkpoint import load_checkpoint, resume_state, save_checkpoint, set_rng_state
@@ -77,10 +83,19 @@ def build_argparser() -> argparse.ArgumentParser:
                         "logits per pixel, pixel-wise cross-entropy on the mask's class indices")
     p.add_argument("--ignore_index", type=int, default=-100,
                    help="label left out of the multi-class loss and Dice (--num_classes > 1)")
-    p.add_argument("--loss", default="ce", choices=["ce", "dice", "ce+dice", "lovasz", "ce+lovasz"],
+    p.add_argument("--loss", default="ce",
+                   choices=["ce", "dice", "ce+dice", "lovasz", "ce+lovasz", "boundary", "ce+boundary"],
                    help="ce: BCEWithLogits (--num_classes 1) / pixel-wise cross-entropy (K > 1); dice: the soft Dice "
                         "loss of sigmoid / softmax; ce+dice: their sum, computed in the passes of ce alone; lovasz: "
-                        "the Lovasz hinge (--num_classes 1) / Lovasz-Softmax (K > 1) loss; ce+lovasz: ce plus that")
+                        "the Lovasz hinge (--num_classes 1) / Lovasz-Softmax (K > 1) loss; ce+lovasz: ce plus that; "
+                        "boundary: the boundary loss on the signed distance map of the masks; ce+boundary: ce plus "
+                        "--boundary_weight times that")
+    p.add_argument("--boundary_weight", type=float, default=0.01,
+                   help="weight A of the boundary term at epoch 0 (--loss ce+boundary)")
+    p.add_argument("--boundary_ramp", type=float, default=0.0,
+                   help="D: the boundary term's weight is A + D * epoch (--loss ce+boundary)")
+    p.add_argument("--boundary_background", type=int, default=1, choices=[0, 1],
+                   help="0: leave class 0 out of the boundary term (K > 1)")
     p.add_argument("--lovasz_weight", type=float, default=1.0, help="weight of the Lovasz term (--loss ce+lovasz)")
     p.add_argument("--lovasz_per_image", type=int, default=None, choices=[0, 1],
                    help="1: rank every sample on its own (default: 1 for --num_classes 1, 0 for K > 1)")
@@ -301,8 +316,16 @@ def build_criterion(args):
                        per_image=per_image)
             return LovaszSoftmaxLoss(**seg) if kind == "lovasz" else CELovaszLoss(lovasz_weight=lw, **seg)
         return LovaszHingeLoss(per_image) if kind == "lovasz" else BCELovaszLoss(per_image, lovasz_weight=lw)
+    if kind in ("boundary", "ce+boundary"):
+        bw, ramp = getattr(args, "boundary_weight", 0.01), getattr(args, "boundary_ramp", 0.0)
+        if not (math.isfinite(bw) and math.isfinite(ramp) and bw >= 0 and ramp >= 0):
+            raise ValueError(f"--boundary_weight and --boundary_ramp must be finite and >= 0, got {bw} and {ramp}")
+        bg = bool(getattr(args, "boundary_background", 1))
+        if kind == "boundary":
+            return BoundaryLoss(args.ignore_index, bg)
+        return CEBoundaryLoss(args.ignore_index, bg, boundary_weight=bw) if K > 1 else BCEBoundaryLoss(boundary_weight=bw)
     if kind not in ("dice", "ce+dice"):
-        raise ValueError(f"--loss must be ce, dice, ce+dice, lovasz or ce+lovasz, got {kind!r}")
+        raise ValueError(f"--loss must be ce, dice, ce+dice, lovasz, ce+lovasz, boundary or ce+boundary, got {kind!r}")
     smooth = getattr(args, "dice_smooth", 1.0)
     if kind == "dice":
         if K > 1:
@@ -314,6 +337,18 @@ def build_criterion(args):
         return CEDiceLoss(ignore_index=args.ignore_index, dice_weight=dw, smooth=smooth,
                           include_background=bool(getattr(args, "dice_background", 1)))
     return BCEDiceLoss(dice_weight=dw, smooth=smooth)
+
+
+def set_boundary_epoch(criterion, args, epoch, device):
+    """--loss ce+boundary: write the boundary term's weight A + D * epoch into the criterion's device scalar (made on
+    the first call), which the loss kernels read -- outside the captured step, so replays follow it.  Any other
+    criterion is left alone."""
+    if not isinstance(criterion, (CEBoundaryLoss, BCEBoundaryLoss)):
+        return
+    w = getattr(args, "boundary_weight", 0.01) + getattr(args, "boundary_ramp", 0.0) * epoch
+    if not torch.is_tensor(criterion.boundary_weight):
+        criterion.boundary_weight = torch.empty(1, dtype=torch.float32, device=device)
+    criterion.boundary_weight.fill_(w)
 
 
 def run(args) -> dict:
@@ -352,6 +387,7 @@ def run(args) -> dict:
         meta = load_checkpoint(ddp, model_filepath, map_location=device, optimizer=optimizer)
         start_epoch = int(meta.get("next_epoch", 0))
         set_rng_state(meta.get("rng"))
+    set_boundary_epoch(criterion, args, start_epoch, device)
     # averaged weights (--ema_decay): the optimizer's device step counter tells a skipped update (the clip hand-off's
     # non-finite norm) from an applied one
     ema = ema_of(args, ddp, optimizer)
@@ -407,6 +443,7 @@ def run(args) -> dict:
     try:
         for epoch in range(start_epoch, args.num_epochs):
             sampler.set_epoch(epoch)
+            set_boundary_epoch(criterion, args, epoch, device)
             t0 = time.time()
             ddp.train()
             loss_sum = torch.zeros((), device=device)

@@ -1,5 +1,5 @@
 // Torch binding of the losses and evaluation counts (kernels/loss.hip, cls_ce.hip, pixel_ce.hip, seg_dice.hip,
-// ohem.hip, lovasz.hip).
+// ohem.hip, lovasz.hip, edt.hip, boundary.hip).
 // softmax_ce_*, bce_*, argmax_correct and dice take their shapes from the caller (NativeBackend) unchecked.
 #include <algorithm>
 #include <cmath>
@@ -439,6 +439,103 @@ void lovasz_hinge_bwd(const at::Tensor& logits, const at::Tensor& target, int N,
                                ptr<float>(dlogits), cur_stream()),
         fn);
 }
+// Exact Euclidean distance transform / signed distance map (edt.hip).  src [N, H, W]: int64 labels of K classes, or
+// with K = 1 an fp32 target (G = {t > 0.5}) or a bool / uint8 mask; phi fp32, d2_in / d2_out int32, each [N, K, H, W]
+// or absent.  The uint16 row plane and the row flags come from the caching allocator per call.
+void edt(const at::Tensor& src, int64_t K, int64_t ignore_index, const c10::optional<at::Tensor>& phi,
+         const c10::optional<at::Tensor>& d2_in, const c10::optional<at::Tensor>& d2_out) {
+  const char* fn = "edt";
+  if (src.dim() != 3 || src.numel() < 1) fail(fn, "src must be [N, H, W] with N, H, W >= 1");
+  const int64_t N = src.size(0), H = src.size(1), W = src.size(2);
+  const at::ScalarType t = src.scalar_type();
+  const int source = t == at::kLong ? 0 : t == at::kFloat ? 1 : (t == at::kBool || t == at::kByte) ? 2 : -1;
+  if (source < 0 || !src.is_cuda() || !src.is_contiguous())
+    fail(fn, "src must be a contiguous int64, fp32, bool or uint8 GPU tensor");
+  if (source != 0 && K != 1) fail(fn, "a target or a mask is one class: K = 1");
+  const int64_t bytes = dlmpi_edt_ws_bytes(N, K, H, W);
+  if (bytes < 0) fail(fn, "served shapes: 1 <= H <= 4096, 1 <= W <= 16384, 1 <= K <= 256");
+  if (!given(phi) && !given(d2_in) && !given(d2_out)) fail(fn, "nothing to write");
+  dense(phi, at::kFloat, N * K * H * W, fn, "phi");
+  dense(d2_in, at::kInt, N * K * H * W, fn, "d2_in");
+  dense(d2_out, at::kInt, N * K * H * W, fn, "d2_out");
+  at::Tensor ws = at::empty({(bytes + 1) / 2}, src.options().dtype(at::kShort));
+  check(dlmpi_edt(src.data_ptr(), source, N, (int)K, (int)H, (int)W, ignore_index, ws.data_ptr(), optr<float>(phi),
+                  optr<int32_t>(d2_in), optr<int32_t>(d2_out), cur_stream()),
+        fn);
+}
+// Boundary loss (boundary.hip).  boundary_weight: a finite float >= 0, or with bw_dev one fp32 on the device that the
+// kernels read; phi fp32 [N * K * HW] (softmax form) / [M] (sigmoid form).
+void boundary_weight_check(double plain, double bw, const c10::optional<at::Tensor>& bw_dev, const char* fn) {
+  if (!std::isfinite(plain) || !std::isfinite(bw) || plain < 0 || bw < 0)
+    fail(fn, "the two loss weights must be finite and >= 0");
+  dense(bw_dev, at::kFloat, 1, fn, "boundary_weight");
+}
+void boundary_softmax_fwd(const at::Tensor& logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                          const at::Tensor& labels, int64_t ignore_index, const at::Tensor& phi,
+                          bool include_background, double ce_weight, double boundary_weight,
+                          const c10::optional<at::Tensor>& bw_dev, at::Tensor lse, at::Tensor loss, at::Tensor den) {
+  const char* fn = "boundary_softmax_fwd";
+  pix_fwd_check(fn, logits, sn, sk, sp, N, K, HW, labels, c10::nullopt, lse, den, nullptr, &loss);
+  boundary_weight_check(ce_weight, boundary_weight, bw_dev, fn);
+  dense(phi, at::kFloat, (int64_t)N * K * HW, fn, "phi");
+  const int64_t nblk = dlmpi_boundary_blocks((int64_t)N * HW);
+  at::Tensor part = at::empty({nblk, 2}, logits.options());
+  at::Tensor cnt = at::empty({nblk}, logits.options().dtype(at::kInt));
+  check(dlmpi_boundary_softmax_fwd(ptr<float>(logits), sn, sk, sp, N, K, HW, ptr<int64_t>(labels), ignore_index,
+                                   ptr<float>(phi), include_background ? 1 : 0, (float)ce_weight,
+                                   (float)boundary_weight, optr<float>(bw_dev), ptr<float>(lse), ptr<float>(part),
+                                   ptr<uint32_t>(cnt), ptr<float>(loss), ptr<float>(den), cur_stream()),
+        fn);
+}
+void boundary_softmax_bwd(const at::Tensor& logits, int64_t sn, int64_t sk, int64_t sp, int N, int K, int64_t HW,
+                          const at::Tensor& labels, int64_t ignore_index, const at::Tensor& phi,
+                          bool include_background, const at::Tensor& lse, const at::Tensor& den,
+                          const c10::optional<at::Tensor>& go, double ce_weight, double boundary_weight,
+                          const c10::optional<at::Tensor>& bw_dev, at::Tensor dlogits) {
+  const char* fn = "boundary_softmax_bwd";
+  pix_bwd_check(fn, logits, sn, sk, sp, N, K, HW, labels, c10::nullopt, lse, den, nullptr, dlogits, go);
+  boundary_weight_check(ce_weight, boundary_weight, bw_dev, fn);
+  dense(phi, at::kFloat, (int64_t)N * K * HW, fn, "phi");
+  check(dlmpi_boundary_softmax_bwd(ptr<float>(logits), sn, sk, sp, N, K, HW, ptr<int64_t>(labels), ignore_index,
+                                   ptr<float>(phi), include_background ? 1 : 0, ptr<float>(lse), ptr<float>(den),
+                                   optr<float>(go), (float)ce_weight, (float)boundary_weight, optr<float>(bw_dev),
+                                   ptr<float>(dlogits), cur_stream()),
+        fn);
+}
+// logits, target, phi: contiguous fp32 of M elements
+void boundary_sigmoid_fwd(const at::Tensor& logits, const at::Tensor& target, const at::Tensor& phi, int64_t M,
+                          double bce_weight, double boundary_weight, const c10::optional<at::Tensor>& bw_dev,
+                          at::Tensor loss, at::Tensor den) {
+  const char* fn = "boundary_sigmoid_fwd";
+  if (M < 1) fail(fn, "M >= 1");
+  dense(logits, at::kFloat, M, fn, "logits");
+  dense(target, at::kFloat, M, fn, "target");
+  dense(phi, at::kFloat, M, fn, "phi");
+  boundary_weight_check(bce_weight, boundary_weight, bw_dev, fn);
+  dense(loss, at::kFloat, 1, fn, "loss");
+  dense(den, at::kFloat, 1, fn, "den");
+  at::Tensor part = at::empty({(int64_t)dlmpi_boundary_blocks(M), 2}, logits.options());
+  check(dlmpi_boundary_sigmoid_fwd(ptr<float>(logits), ptr<float>(target), ptr<float>(phi), M, (float)bce_weight,
+                                   (float)boundary_weight, optr<float>(bw_dev), ptr<float>(part), ptr<float>(loss),
+                                   ptr<float>(den), cur_stream()),
+        fn);
+}
+void boundary_sigmoid_bwd(const at::Tensor& logits, const at::Tensor& target, const at::Tensor& phi, int64_t M,
+                          const c10::optional<at::Tensor>& go, double bce_weight, double boundary_weight,
+                          const c10::optional<at::Tensor>& bw_dev, at::Tensor dlogits) {
+  const char* fn = "boundary_sigmoid_bwd";
+  if (M < 1) fail(fn, "M >= 1");
+  dense(logits, at::kFloat, M, fn, "logits");
+  dense(target, at::kFloat, M, fn, "target");
+  dense(phi, at::kFloat, M, fn, "phi");
+  dense(dlogits, at::kFloat, M, fn, "dlogits");
+  boundary_weight_check(bce_weight, boundary_weight, bw_dev, fn);
+  dense(go, at::kFloat, 1, fn, "go");
+  check(dlmpi_boundary_sigmoid_bwd(ptr<float>(logits), ptr<float>(target), ptr<float>(phi), M, optr<float>(go),
+                                   (float)bce_weight, (float)boundary_weight, optr<float>(bw_dev),
+                                   ptr<float>(dlogits), cur_stream()),
+        fn);
+}
 }  // namespace
 
 void register_loss(pybind11::module& m) {
@@ -477,6 +574,13 @@ void register_loss(pybind11::module& m) {
   m.def("lovasz_softmax_bwd", &lovasz_softmax_bwd);
   m.def("lovasz_hinge_fwd", &lovasz_hinge_fwd);
   m.def("lovasz_hinge_bwd", &lovasz_hinge_bwd);
+  m.def("edt_strip", []() { return dlmpi_edt_strip(); });
+  m.def("edt_strip_rows", []() { return dlmpi_edt_strip_rows(); });
+  m.def("edt", &edt);
+  m.def("boundary_softmax_fwd", &boundary_softmax_fwd);
+  m.def("boundary_softmax_bwd", &boundary_softmax_bwd);
+  m.def("boundary_sigmoid_fwd", &boundary_sigmoid_fwd);
+  m.def("boundary_sigmoid_bwd", &boundary_sigmoid_bwd);
 }
 
 }  // namespace dlmpi_ext

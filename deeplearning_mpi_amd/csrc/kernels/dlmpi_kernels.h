@@ -506,6 +506,38 @@ hipError_t dlmpi_lovasz_hinge_fwd(const float* logits, const float* target, int 
 hipError_t dlmpi_lovasz_hinge_bwd(const float* logits, const float* target, int N, int64_t HW, int per_image,
                                   const float* g, const float* coef, const float* go, float bce_weight,
                                   float lovasz_weight, float* dlogits, hipStream_t s);
+// Exact Euclidean distance transform and signed distance map (edt.hip; the definition is at the top of that file).
+// source: 0 int64 labels [N][H][W] of K classes, 1 fp32 target (K = 1, G = {t > 0.5}), 2 uint8 mask (K = 1,
+// G = {!= 0}).  Served: 1 <= H <= 4096, 1 <= W <= 16384, K <= 256 (dlmpi_edt_ok).  ws: dlmpi_edt_ws_bytes bytes
+// (-1: a refused shape), 2-byte aligned, nothing in it needs zeroing.  phi fp32, d2_in / d2_out int32 (INT32_MAX: no
+// such pixel), each [N][K][H][W] or null.  No host read, no atomics.
+int dlmpi_edt_strip();        // columns of the widest strip of the column pass
+int dlmpi_edt_strip_rows();   // rows up to which the strip is that wide; it halves with every doubling beyond
+int dlmpi_edt_ok(int64_t N, int64_t K, int64_t H, int64_t W);
+int64_t dlmpi_edt_ws_bytes(int64_t N, int64_t K, int64_t H, int64_t W);
+hipError_t dlmpi_edt(const void* src, int source, int64_t N, int K, int H, int W, int64_t ignore_index, void* ws,
+                     float* phi, int32_t* d2_in, int32_t* d2_out, hipStream_t s);
+// Boundary loss (boundary.hip): loss = ce_weight * (plain unweighted CE / BCE) + boundary_weight * B with B the mean
+// of p * phi over the valid pixels and the classes (from 1 on without the background); phi fp32 [N][K][HW] plain
+// NCHW.  boundary_weight = *bw_dev where given (one fp32 on the device), else bw_host.  part fp32
+// [2 * dlmpi_boundary_blocks(N * HW)], cnt uint32 [dlmpi_boundary_blocks(N * HW)]; den = n_valid.
+int dlmpi_boundary_blocks(int64_t M);
+hipError_t dlmpi_boundary_softmax_fwd(const float* logits, int64_t sn, int64_t sk, int64_t sp, int N, int K,
+                                      int64_t HW, const int64_t* labels, int64_t ignore_index, const float* phi,
+                                      int include_background, float ce_weight, float bw_host, const float* bw_dev,
+                                      float* lse, float* part, uint32_t* cnt, float* loss, float* den, hipStream_t s);
+hipError_t dlmpi_boundary_softmax_bwd(const float* logits, int64_t sn, int64_t sk, int64_t sp, int N, int K,
+                                      int64_t HW, const int64_t* labels, int64_t ignore_index, const float* phi,
+                                      int include_background, const float* lse, const float* den, const float* go,
+                                      float ce_weight, float bw_host, const float* bw_dev, float* dlogits,
+                                      hipStream_t s);
+// sigmoid form: contiguous logits, float targets and phi of M elements
+hipError_t dlmpi_boundary_sigmoid_fwd(const float* logits, const float* target, const float* phi, int64_t M,
+                                      float bce_weight, float bw_host, const float* bw_dev, float* part, float* loss,
+                                      float* den, hipStream_t s);
+hipError_t dlmpi_boundary_sigmoid_bwd(const float* logits, const float* target, const float* phi, int64_t M,
+                                      const float* go, float bce_weight, float bw_host, const float* bw_dev,
+                                      float* dlogits, hipStream_t s);
 
 // eval
 hipError_t dlmpi_argmax_correct(const float* logits, int ldl, const int64_t* labels, int N, int K, int* correct,

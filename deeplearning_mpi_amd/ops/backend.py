@@ -665,6 +665,69 @@ class NativeBackend:
                                 float(bce_weight), float(lovasz_weight), d)
         return d
 
+    # Exact Euclidean distance transform and the boundary loss (edt.hip, boundary.hip).  Served: H <= 4096,
+    # W <= 16384; workspace 2 bytes per pixel and class (+ 1 per row and class) beside the 4 of phi.
+    @property
+    def edt_strip(self):
+        """Columns of the column pass's widest strip (the widths around it are the edge cases of its tests)."""
+        return self.C.edt_strip()
+
+    @property
+    def edt_strip_rows(self):
+        """Rows up to which the strip is ``edt_strip`` wide; beyond, it halves with every doubling."""
+        return self.C.edt_strip_rows()
+
+    def edt_squared(self, mask):
+        """bool [P, H, W] -> int32 [P, H, W]: the squared distance to the nearest True pixel (INT32_MAX: none)."""
+        P, H, W = mask.shape
+        d2 = torch.empty(P, 1, H, W, dtype=torch.int32, device=mask.device)
+        self.C.edt(mask.contiguous(), 1, 0, None, d2, None)
+        return d2.view(P, H, W)
+
+    def signed_distance(self, labels, num_classes=1, ignore_index=-100):
+        """int64 labels [N, H, W] -> phi fp32 [N, K, H, W]; a float target (fg = t > 0.5) -> phi [N, H, W]."""
+        N, H, W = labels.shape
+        K = num_classes if labels.dtype == torch.int64 else 1
+        phi = torch.empty(N, K, H, W, dtype=torch.float32, device=labels.device)
+        self.C.edt(labels.contiguous(), K, int(ignore_index), phi, None, None)
+        return phi if labels.dtype == torch.int64 else phi.view(N, H, W)
+
+    @staticmethod
+    def _boundary_weight(w):   # -> (the host float, the device scalar or None)
+        return (0.0, w) if torch.is_tensor(w) else (float(w), None)
+
+    def boundary_softmax_fwd(self, logits, labels, phi, ignore_index=-100, include_background=True, ce_weight=0.0,
+                             boundary_weight=1.0):
+        """-> (ce_weight * CE + boundary_weight * B, lse [N*H*W], den = n_valid)."""
+        N, K, H, W = logits.shape
+        lse, loss, den = self._pixel_fwd_out(logits)
+        self.C.boundary_softmax_fwd(logits, *pixel_strides(logits), N, K, H * W, labels, int(ignore_index), phi,
+                                    bool(include_background), float(ce_weight), *self._boundary_weight(boundary_weight),
+                                    lse, loss, den)
+        return loss, lse, den
+
+    def boundary_softmax_bwd(self, logits, labels, phi, lse, den, go, ignore_index=-100, include_background=True,
+                             ce_weight=0.0, boundary_weight=1.0):
+        N, K, H, W = logits.shape
+        d = self._pixel_dlogits(logits)
+        self.C.boundary_softmax_bwd(logits, *pixel_strides(logits), N, K, H * W, labels, int(ignore_index), phi,
+                                    bool(include_background), lse, den, go, float(ce_weight),
+                                    *self._boundary_weight(boundary_weight), d)
+        return d
+
+    def boundary_sigmoid_fwd(self, logits, target, phi, bce_weight=0.0, boundary_weight=1.0):
+        """logits, target, phi fp32 contiguous of one shape -> bce_weight * BCE + boundary_weight * mean(p phi)."""
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        self.C.boundary_sigmoid_fwd(logits, target, phi, logits.numel(), float(bce_weight),
+                                    *self._boundary_weight(boundary_weight), loss, loss.new_empty(1))
+        return loss
+
+    def boundary_sigmoid_bwd(self, logits, target, phi, go, bce_weight=0.0, boundary_weight=1.0):
+        d = torch.empty_like(logits, memory_format=torch.contiguous_format)
+        self.C.boundary_sigmoid_bwd(logits, target, phi, logits.numel(), go, float(bce_weight),
+                                    *self._boundary_weight(boundary_weight), d)
+        return d
+
     def bce_fwd(self, logits, target):
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
         self.C.bce_fwd(logits, 1, target, logits.numel(), loss)
@@ -1365,6 +1428,96 @@ class RefBackend:
         if bce_weight != 0:
             d = d + (torch.sigmoid(x) - t) * (bce_weight * go / x.numel())
         return d.view(logits.shape)
+
+    # Exact Euclidean distance transform and the boundary loss: the definition of csrc/kernels/edt.hip and
+    # boundary.hip in plain torch (the CPU path)
+    edt_strip, edt_strip_rows = 64, 512   # the native column pass's, so that tests take the same sizes on either backend
+    _EDT_INF = 2 ** 31 - 1
+
+    def edt_squared(self, mask):
+        """bool [P, H, W] -> int32 [P, H, W]: an exact separable minimum, the column pass in chunks of rows."""
+        P, H, W = mask.shape
+        far = 1 << 20
+        idx = torch.arange(W, device=mask.device).expand(P, H, W)
+        last = torch.where(mask, idx, torch.full_like(idx, -far)).cummax(2).values
+        nxt = torch.where(mask, idx, torch.full_like(idx, far)).flip(2).cummin(2).values.flip(2)
+        f = torch.minimum(idx - last, nxt - idx)                  # along the row; >= far: no True pixel in it
+        f2 = torch.where(f >= far // 2, torch.full_like(f, 1 << 40), f * f)
+        ys = torch.arange(H, device=mask.device)
+        out = torch.empty(P, H, W, dtype=torch.int64, device=mask.device)
+        rows = max(1, (1 << 22) // max(1, P * H * W))
+        for y0 in range(0, H, rows):
+            dy = ys[y0:y0 + rows, None] - ys[None, :]             # [rows, H]
+            out[:, y0:y0 + rows] = (f2[:, None] + (dy * dy)[None, :, :, None]).min(2).values
+        return out.clamp_max(self._EDT_INF).to(torch.int32)
+
+    def signed_distance(self, labels, num_classes=1, ignore_index=-100):
+        if labels.dtype == torch.int64:
+            keep = self._pix_keep(labels, num_classes, ignore_index).unsqueeze(1)
+            m = (labels.unsqueeze(1) == torch.arange(num_classes, device=labels.device).view(1, -1, 1, 1)) & keep
+        else:
+            m = (labels > 0.5).unsqueeze(1)
+        N, K, H, W = m.shape
+        d_in, d_out = (self.edt_squared(t.reshape(N * K, H, W)).view(N, K, H, W) for t in (m, ~m))
+        d2 = torch.where(m, d_out, d_in)
+        root = d2.double().sqrt()
+        phi = torch.where(d2 == self._EDT_INF, torch.zeros_like(root), torch.where(m, 1 - root, root)).to(self.dt)
+        return phi if labels.dtype == torch.int64 else phi.view(N, H, W)
+
+    @staticmethod
+    def _boundary_classes(K, include_background, like):
+        c = torch.ones(K, dtype=like.dtype, device=like.device)
+        if not include_background:
+            c[0] = 0
+        return c.view(1, K, 1, 1), K - (0 if include_background else 1)
+
+    def boundary_softmax_fwd(self, logits, labels, phi, ignore_index=-100, include_background=True, ce_weight=0.0,
+                             boundary_weight=1.0):
+        x = logits.to(self.dt)
+        N, K, H, W = x.shape
+        keep = self._pix_keep(labels, K, ignore_index)
+        lse = torch.logsumexp(x, 1)
+        cls, nc = self._boundary_classes(K, include_background, x)
+        nv = keep.sum().to(self.dt)
+        b = (torch.exp(x - lse.unsqueeze(1)) * phi.to(self.dt) * cls * keep.unsqueeze(1)).sum()
+        loss = boundary_weight * torch.where(nv > 0, b / (nv * nc).clamp_min(1), torch.zeros_like(b))
+        loss = loss.reshape(())
+        if ce_weight != 0:
+            loss = loss + ce_weight * self.pixel_ce_fwd(logits, labels, None, ignore_index)[0]
+        return loss, lse.reshape(-1), nv.reshape(1)
+
+    def boundary_softmax_bwd(self, logits, labels, phi, lse, den, go, ignore_index=-100, include_background=True,
+                             ce_weight=0.0, boundary_weight=1.0):
+        x = logits.to(self.dt)
+        N, K, H, W = x.shape
+        keep = self._pix_keep(labels, K, ignore_index).unsqueeze(1)
+        cls, nc = self._boundary_classes(K, include_background, x)
+        p = torch.exp(x - lse.view(N, 1, H, W))
+        go = go if go is not None else 1.0
+        a = phi.to(self.dt) * cls * (boundary_weight * go / (den.clamp_min(1) * nc))
+        d = p * (a - (a * p).sum(1, keepdim=True))
+        if ce_weight != 0:
+            oh = F.one_hot(labels.clamp(0, K - 1), K).permute(0, 3, 1, 2).to(self.dt)
+            d = d + (p - oh) * (ce_weight * go / den)
+        out = torch.empty_like(logits, dtype=self.dt)
+        out.copy_(torch.where(keep, d, torch.zeros((), dtype=self.dt, device=x.device)))
+        return out
+
+    def boundary_sigmoid_fwd(self, logits, target, phi, bce_weight=0.0, boundary_weight=1.0):
+        x = logits.to(self.dt)
+        loss = (boundary_weight * (torch.sigmoid(x) * phi.to(self.dt)).mean()).reshape(())
+        if bce_weight != 0:
+            loss = loss + bce_weight * F.binary_cross_entropy_with_logits(x, target.to(self.dt))
+        return loss
+
+    def boundary_sigmoid_bwd(self, logits, target, phi, go, bce_weight=0.0, boundary_weight=1.0):
+        x = logits.to(self.dt)
+        p = torch.sigmoid(x)
+        go = go if go is not None else 1.0
+        d = phi.to(self.dt) * p * (1 - p) * (boundary_weight * go / x.numel())
+        if bce_weight != 0:
+            d = d + (p - target.to(self.dt)) * (bce_weight * go / x.numel())
+        return d
 
     def bce_fwd(self, logits, target):
         return F.binary_cross_entropy_with_logits(logits.to(self.dt), target.to(self.dt))

@@ -459,6 +459,195 @@ class LovaszHingeLoss(BCELovaszLoss):
         super().__init__(per_image, 0.0, 1.0)
 
 
+def edt_squared(mask):
+    """Exact squared Euclidean distance transform: bool ``mask`` [..., H, W] -> int32 of that shape, the squared
+    distance ``dy^2 + dx^2`` of every pixel to the nearest True pixel of its plane (0 on the True pixels),
+    ``INT32_MAX`` where the plane has none.  On the GPU a separable integer transform (csrc/kernels/edt.hip: H <= 4096,
+    W <= 16384), no host synchronisation."""
+    if mask.dim() < 2 or mask.dtype != torch.bool:
+        raise ValueError(f"edt_squared takes a bool mask [..., H, W], got {mask.dtype} {tuple(mask.shape)}")
+    be = _be(mask.device)
+    return be.edt_squared(mask.reshape(-1, *mask.shape[-2:])).view(mask.shape)
+
+
+def signed_distance_map(labels, num_classes=None, ignore_index=-100):
+    """The signed distance maps of the boundary loss (Kervadec et al., MIDL 2019, ``one_hot2dist``).  int64 labels
+    [N, H, W] with ``num_classes`` K -> fp32 [N, K, H, W]; a float target [N, H, W] (fg = t > 0.5) -> fp32 [N, H, W].
+    With G the pixels of the class (ignored and out-of-range pixels are in no G): +sqrt(d2) to the nearest pixel of G
+    outside it, 1 - sqrt(d2) to the nearest pixel outside G inside it (inner border 0, interior negative), 0 for a
+    class that is absent from the sample or fills it.  The distances are exact integers, the root is rounded once."""
+    if labels.dim() != 3 or not (labels.dtype == torch.int64 or labels.is_floating_point()):
+        raise ValueError(f"signed_distance_map takes int64 labels or a float target [N, H, W], got {labels.dtype} "
+                         f"{tuple(labels.shape)}")
+    be = _be(labels.device)
+    if labels.dtype != torch.int64:
+        return be.signed_distance(labels.to(torch.float32).contiguous())
+    if num_classes is None or not 1 <= int(num_classes) <= 256:
+        raise ValueError(f"int64 labels need num_classes in 1..256, got {num_classes}")
+    return be.signed_distance(labels.contiguous(), int(num_classes), int(ignore_index))
+
+
+class _BoundarySoftmax(torch.autograd.Function):
+    """ce_weight * pixel-wise cross-entropy + boundary_weight * boundary loss (csrc/kernels/boundary.hip): logits
+    read in place, the gradient in their strides; ``bw`` is a float or a one-element device tensor that both passes
+    read in place."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, phi, ignore_index, include_background, ce_weight, bw):
+        be, x, labels, _ = _pixel_inputs(logits, labels, None)
+        loss, lse, den = be.boundary_softmax_fwd(x, labels, phi, ignore_index, include_background, ce_weight, bw)
+        ctx.save_for_backward(x, labels, phi, lse, den)
+        ctx.args, ctx.in_dtype = (ignore_index, include_background, ce_weight, bw), logits.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, go):
+        x, labels, phi, lse, den = ctx.saved_tensors
+        be = _be(x.device, x.dtype)
+        d = be.boundary_softmax_bwd(x, labels, phi, lse, den, go.reshape(1).to(be.dt).contiguous(), *ctx.args)
+        return (d.to(ctx.in_dtype),) + (None,) * 6
+
+
+class _BoundarySigmoid(torch.autograd.Function):
+    """bce_weight * BCE-with-logits + boundary_weight * mean(sigmoid(x) phi): contiguous logits, float targets."""
+
+    @staticmethod
+    def forward(ctx, logits, target, phi, bce_weight, bw):
+        be = _be(logits.device, logits.dtype)
+        x = logits.contiguous().to(be.dt)
+        target = target.contiguous().to(be.dt)
+        loss = be.boundary_sigmoid_fwd(x, target, phi, bce_weight, bw)
+        ctx.save_for_backward(x, target, phi)
+        ctx.args, ctx.in_dtype = (bce_weight, bw), logits.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, go):
+        x, target, phi = ctx.saved_tensors
+        be = _be(x.device, x.dtype)
+        d = be.boundary_sigmoid_bwd(x, target, phi, go.reshape(1).to(be.dt).contiguous(), *ctx.args)
+        return d.view(x.shape).to(ctx.in_dtype), None, None, None, None
+
+
+def _check_boundary_weights(plain, bw, names, device=None):
+    """-> (plain weight, boundary weight: a float or a one-element fp32 tensor on ``device``)."""
+    plain = float(plain)
+    if not math.isfinite(plain) or plain < 0:
+        raise ValueError(f"{names[0]} must be finite and >= 0, got {plain}")
+    if torch.is_tensor(bw):
+        if bw.numel() != 1 or bw.dtype != torch.float32 or (device is not None and bw.device != device):
+            raise ValueError(f"a tensor {names[1]} is one fp32 element on the device of the logits")
+        return plain, bw
+    bw = float(bw)
+    if not math.isfinite(bw) or bw < 0:
+        raise ValueError(f"{names[1]} must be finite and >= 0, got {bw}")
+    if plain == 0 and bw == 0:
+        raise ValueError(f"{names[0]} and {names[1]} must not both be 0")
+    return plain, bw
+
+
+def _boundary(logits, target, ignore_index, include_background, dist, plain_weight, boundary_weight, names):
+    plain_weight, bw = _check_boundary_weights(plain_weight, boundary_weight, names, logits.device)
+    be = _be(logits.device, logits.dtype)
+    if target.dtype == torch.int64:
+        if logits.dim() != 4:
+            raise ValueError(f"the boundary loss takes [N, K, H, W] logits with int64 labels, got {tuple(logits.shape)}")
+        _check_pixel_args(logits, target)
+        if not include_background and logits.shape[1] < 2:
+            raise ValueError("include_background=False needs at least two classes")
+        if not torch.is_tensor(bw) and bw == 0:
+            loss = _PixelCE.apply(logits, target, None, int(ignore_index))
+            return loss if plain_weight == 1 else loss * plain_weight
+        shape = tuple(logits.shape)
+        if dist is None:
+            dist = be.signed_distance(target.contiguous(), shape[1], int(ignore_index))
+        elif tuple(dist.shape) != shape:
+            raise ValueError(f"dist must be the signed_distance_map of the labels, {shape}, got {tuple(dist.shape)}")
+        return _BoundarySoftmax.apply(logits, target, dist.to(be.dt).contiguous(), int(ignore_index),
+                                      bool(include_background), plain_weight, bw)
+    if logits.dim() == target.dim() + 1 and logits.shape[1] == 1:
+        logits = logits.squeeze(1)
+    if target.dim() != 3 or logits.shape != target.shape or not target.is_floating_point():
+        raise ValueError(f"the binary boundary loss takes logits [N, H, W] or [N, 1, H, W] and a float target "
+                         f"[N, H, W], got {tuple(logits.shape)} and {target.dtype} {tuple(target.shape)}")
+    if not torch.is_tensor(bw) and bw == 0:
+        loss = _BCE.apply(logits, target)
+        return loss if plain_weight == 1 else loss * plain_weight
+    if dist is None:
+        dist = be.signed_distance(target.to(torch.float32).contiguous())
+    elif dist.shape != target.shape:
+        raise ValueError(f"dist must be the signed_distance_map of the target, {tuple(target.shape)}, got "
+                         f"{tuple(dist.shape)}")
+    return _BoundarySigmoid.apply(logits, target, dist.to(be.dt).contiguous(), plain_weight, bw)
+
+
+def boundary_loss(logits, target, ignore_index=-100, include_background=True, dist=None):
+    """The boundary (surface) loss of Kervadec et al. (MIDL 2019).  int64 ``target`` [N, H, W] with [N, K, H, W]
+    logits: B = sum over the valid pixels and the classes C of softmax_c * phi_c / (n_valid |C|), phi =
+    :func:`signed_distance_map` of the labels, C every class or 1..K-1 without the background, a pixel valid as in
+    :func:`cross_entropy`; nothing valid: loss 0, zero gradient; invalid pixels get an exact zero gradient.  A float
+    ``target`` [N, H, W] with logits [N, H, W] or [N, 1, H, W]: B = mean(sigmoid(x) * phi) with phi the map of
+    t > 0.5.  ``dist`` takes a precomputed :func:`signed_distance_map` (static masks pay for the transform once);
+    without it the map is computed on the device in the same stream (csrc/kernels/edt.hip), so the loss needs no host
+    synchronisation and captures into a graph with its labels."""
+    return _boundary(logits, target, ignore_index, include_background, dist, 0.0, 1.0, ("ce_weight", "boundary_weight"))
+
+
+def ce_boundary_loss(logits, labels, ignore_index=-100, include_background=True, dist=None, ce_weight=1.0,
+                     boundary_weight=0.01):
+    """``ce_weight * CE + boundary_weight * boundary_loss`` with CE the plain unweighted :func:`cross_entropy` over
+    the valid pixels, in one fused forward and one backward pass.  ``boundary_weight`` is a float or a one-element fp32
+    tensor on the device, which the kernels read (a rebalancing schedule can then move under graph replay); a float 0
+    is :func:`cross_entropy` itself (the plain kernels), a tensor always takes the fused path."""
+    return _boundary(logits, labels, ignore_index, include_background, dist, ce_weight, boundary_weight,
+                     ("ce_weight", "boundary_weight"))
+
+
+def bce_boundary_loss(logits, target, dist=None, bce_weight=1.0, boundary_weight=0.01):
+    """``bce_weight * BCE + boundary_weight * boundary_loss`` for a float target; ``boundary_weight`` as
+    :func:`ce_boundary_loss`, a float 0 is :func:`bce_with_logits` itself."""
+    if not target.is_floating_point():
+        raise ValueError(f"bce_boundary_loss takes a float target, got {target.dtype}")
+    return _boundary(logits, target, -100, True, dist, bce_weight, boundary_weight, ("bce_weight", "boundary_weight"))
+
+
+class CEBoundaryLoss(nn.Module):
+    """:func:`ce_boundary_loss`.  ``boundary_weight`` may be replaced by a one-element device tensor at any time."""
+
+    def __init__(self, ignore_index=-100, include_background=True, ce_weight=1.0, boundary_weight=0.01):
+        super().__init__()
+        _check_boundary_weights(ce_weight, boundary_weight, ("ce_weight", "boundary_weight"))
+        self.ignore_index, self.include_background = ignore_index, include_background
+        self.ce_weight, self.boundary_weight = ce_weight, boundary_weight
+
+    def forward(self, logits, labels, dist=None):
+        return ce_boundary_loss(logits, labels, self.ignore_index, self.include_background, dist, self.ce_weight,
+                                self.boundary_weight)
+
+
+class BCEBoundaryLoss(nn.Module):
+    """:func:`bce_boundary_loss`; ``boundary_weight`` as :class:`CEBoundaryLoss`."""
+
+    def __init__(self, bce_weight=1.0, boundary_weight=0.01):
+        super().__init__()
+        _check_boundary_weights(bce_weight, boundary_weight, ("bce_weight", "boundary_weight"))
+        self.bce_weight, self.boundary_weight = bce_weight, boundary_weight
+
+    def forward(self, logits, target, dist=None):
+        return bce_boundary_loss(logits, target, dist, self.bce_weight, self.boundary_weight)
+
+
+class BoundaryLoss(nn.Module):
+    """:func:`boundary_loss`, either form by the target's dtype."""
+
+    def __init__(self, ignore_index=-100, include_background=True):
+        super().__init__()
+        self.ignore_index, self.include_background = ignore_index, include_background
+
+    def forward(self, logits, target, dist=None):
+        return boundary_loss(logits, target, self.ignore_index, self.include_background, dist)
+
+
 class _PixelCEDice(torch.autograd.Function):
     """ce_weight * pixel-wise cross-entropy + dice_weight * soft Dice in the passes of _PixelCE: one fused
     forward, one finish, one fused backward; logits read in place, gradient in their strides."""
