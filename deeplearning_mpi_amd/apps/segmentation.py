@@ -57,7 +57,8 @@ from ..data import (CarvanaDataset, DeviceBatches, DeviceCachedDataset, DeviceSe
 from ..models import UNet
 from ..ops import (BCEBoundaryLoss, BCEDiceLoss, BCELovaszLoss, BCEWithLogitsLoss, BoundaryLoss, CEBoundaryLoss,
                    CEDiceLoss, CELovaszLoss, CrossEntropyLoss, DiceLoss, LovaszHingeLoss, LovaszSoftmaxLoss,
-                   OHEMBCEWithLogitsLoss, OHEMCrossEntropyLoss, backward, dice_multiclass, dice_per_sample)
+                   OHEMBCEWithLogitsLoss, OHEMCrossEntropyLoss, backward, dice_multiclass, dice_per_sample,
+                   surface_distances)
 from ..optim import LAMB, Adam, clip_grad_norm_
 from ..utils.graphs import CapturedStep
 from ..utils.checkpoint import load_checkpoint, resume_state, save_checkpoint, set_rng_state
@@ -146,6 +147,11 @@ def build_argparser() -> argparse.ArgumentParser:
                    help="elastic deformation: deviation of the B-spline control points in source pixels (0: none)")
     p.add_argument("--aug_elastic_grid", type=int, default=3, metavar="G", help="cells per axis of the elastic lattice")
     p.add_argument("--aug_elastic_prob", type=float, default=1.0, help="probability that a sample is deformed")
+    p.add_argument("--eval_surface", type=int, default=0, choices=[0, 1],
+                   help="1: every evaluation also reports the surface distances of the argmax against the masks, the "
+                        "Hausdorff percentile (HD95) and the average symmetric surface distance (ASSD), in pixels")
+    p.add_argument("--surface_percentile", type=float, default=95.0, metavar="P",
+                   help="percentile of the Hausdorff distance that --eval_surface reports, in (0, 100]")
     add_layerwise_args(p, "adam", "lamb")
     p.add_argument("--weight_decay", type=float, default=None,
                    help="weight decay (default: 0 for adam, 0.01 for lamb)")
@@ -181,21 +187,34 @@ class RankLog:
 
 
 @torch.no_grad()
-def evaluate_model(model, device, test_loader, num_classes=1, ignore_index=-100) -> float:
+def evaluate_model(model, device, test_loader, num_classes=1, ignore_index=-100, surface_percentile=None):
+    """-> the mean Dice; with ``surface_percentile`` P -> (that, {"hd95", "assd", "undefined"}): the means of the
+    P-th percentile Hausdorff distance and of the ASSD (ops.surface_distances) over the samples and foreground classes
+    where they are finite, and the number of rows where they are not (a class without an edge in pred or in gt).  The
+    sums stay on the device; they are read once, after the last batch."""
     model.eval()
     scores = []
+    surf = 0.0   # becomes the device vector {sum HD-P, sum ASSD, finite rows, the other rows}
     for batch in test_loader:
         images = batch["image"].to(device, dtype=torch.float32)
+        masks = batch["mask"].to(device, dtype=torch.int64 if num_classes > 1 else torch.float32)
+        pred = model(images)
         if num_classes > 1:
-            masks = batch["mask"].to(device, dtype=torch.int64)
-            scores.append(dice_multiclass(model(images), masks, ignore_index))
+            scores.append(dice_multiclass(pred, masks, ignore_index))
         else:
-            masks = batch["mask"].to(device, dtype=torch.float32)
-            scores.append(dice_per_sample(model(images), masks))
+            scores.append(dice_per_sample(pred, masks))
+        if surface_percentile is not None:
+            m = surface_distances(pred, masks, ignore_index, surface_percentile)[0][:, min(1, num_classes - 1):]
+            m = m[..., 1:].double().reshape(-1, 2)
+            ok = torch.isfinite(m).all(1)
+            surf = surf + torch.cat([torch.where(ok[:, None], m, torch.zeros_like(m)).sum(0), ok.sum()[None],
+                                     (~ok).sum()[None]])
     model.train()
-    if not scores:
-        return 0.0
-    return torch.cat(scores).mean().item()
+    dice = torch.cat(scores).mean().item() if scores else 0.0
+    if surface_percentile is None:
+        return dice
+    hd, assd, n, bad = surf.tolist() if scores else (0.0, 0.0, 0, 0)
+    return dice, {"hd95": hd / n if n else math.nan, "assd": assd / n if n else math.nan, "undefined": int(bad)}
 
 
 def seg_aug_config(args) -> SegAugConfig:
@@ -415,10 +434,36 @@ def run(args) -> dict:
             state["ema"] = ema.state_dict()
         save_checkpoint(ddp, model_filepath, optimizer=optimizer, extra=state, rank=rank)
 
-    def ema_dice():
+    surface_p = getattr(args, "surface_percentile", 95.0) if getattr(args, "eval_surface", 0) else None
+
+    surface_lines = []
+
+    def evaluate(where, key=""):
+        """Dice of the model as it stands.  --eval_surface 1: also the surface distances, into history[key + "hd95" /
+        "assd"] (a list per epoch, one value for the final evaluation) and a line that surface_report prints."""
+        if surface_p is None:
+            return evaluate_model(model, device, test_loader, K, args.ignore_index)
+        dice, sd = evaluate_model(model, device, test_loader, K, args.ignore_index, surface_p)
+        surface_lines.append(f"{where}HD{surface_p:g}: {sd['hd95']:.4f} | ASSD: {sd['assd']:.4f} | "
+                             f"undefined: {sd['undefined']}")
+        for name in ("hd95", "assd"):
+            if key.startswith("final_"):
+                history[key + name] = sd[name]
+            else:
+                history.setdefault(key + name, []).append(sd[name])
+        return dice
+
+    def surface_report():
+        """Print and log the surface line of the evaluation just made, after its Dice line."""
+        while surface_lines:
+            line = surface_lines.pop(0)
+            print(line)
+            log(line)
+
+    def ema_dice(where, key):
         """Dice of the averaged model; its weights go next to the trained ones in the reference's layout."""
         with ema.applied():
-            d = evaluate_model(model, device, test_loader, K, args.ignore_index)
+            d = evaluate(where + "EMA ", key + "ema_")
             save_checkpoint(ddp, ema_path(model_filepath), rank=rank)
         return d
 
@@ -437,6 +482,8 @@ def run(args) -> dict:
     if args.benchmark_steps:
         return benchmark(args, train_step, captured, x_static, y_static, comm, device)
     history = {"loss": [], "dice": []}
+    if surface_p is not None:
+        history.update(hd95=[], assd=[])
     if rank == 0:
         print(f"Logging training progress to: {log.path}")
     log(f"Started training at {datetime.now()}")
@@ -468,23 +515,25 @@ def run(args) -> dict:
             log(f"Epoch {epoch + 1} | Loss: {avg_loss:.4f} | Duration: {time.time() - t0:.2f}s")
             if (epoch + 1) % args.eval_every == 0 and rank == 0:
                 state = resume_state(epoch + 1)   # epoch-boundary RNG states, taken before evaluating
-                dice = evaluate_model(model, device, test_loader, K, args.ignore_index)
+                dice = evaluate(f"Epoch {epoch + 1} | ")
                 save(state)
                 print("-" * 75)
                 print(f"Epoch {epoch + 1} Dice Score: {dice:.4f}")
                 print("-" * 75)
                 log(f"Epoch {epoch + 1} | Dice Score: {dice:.4f}")
                 history["dice"].append(dice)
+                surface_report()
                 if ema is not None:
-                    d = ema_dice()
+                    d = ema_dice(f"Epoch {epoch + 1} | ", "")
                     print(f"Epoch {epoch + 1} EMA Dice Score: {d:.4f}")
                     print("-" * 75)
                     log(f"Epoch {epoch + 1} | EMA Dice Score: {d:.4f}")
                     history.setdefault("ema_dice", []).append(d)
+                    surface_report()
         if rank == 0:
             print("\n" + "=" * 80 + "\nTRAINING COMPLETED - FINAL EVALUATION\n" + "=" * 80)
             state = resume_state(args.num_epochs)
-            final = evaluate_model(model, device, test_loader, K, args.ignore_index)
+            final = evaluate("Final ", "final_")
             save(state)
             print(f"FINAL DICE COEFFICIENT: {final:.4f}\n" + "=" * 80 + "\n")
             log("=" * 80)
@@ -496,10 +545,12 @@ def run(args) -> dict:
             log(f"Model saved to: {model_filepath}")
             log("=" * 80)
             history["final_dice"] = final
+            surface_report()
             if ema is not None:
-                history["final_ema_dice"] = ema_dice()
+                history["final_ema_dice"] = ema_dice("Final ", "final_")
                 print(f"FINAL EMA DICE COEFFICIENT: {history['final_ema_dice']:.4f}")
                 log(f"Final EMA Dice Coefficient: {history['final_ema_dice']:.4f}")
+                surface_report()
     finally:
         parallel.destroy_distributed()
     return history

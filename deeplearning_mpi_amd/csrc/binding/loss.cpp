@@ -1,5 +1,5 @@
 // Torch binding of the losses and evaluation counts (kernels/loss.hip, cls_ce.hip, pixel_ce.hip, seg_dice.hip,
-// ohem.hip, lovasz.hip, edt.hip, boundary.hip).
+// ohem.hip, lovasz.hip, edt.hip, boundary.hip, surface.hip).
 // softmax_ce_*, bce_*, argmax_correct and dice take their shapes from the caller (NativeBackend) unchecked.
 #include <algorithm>
 #include <cmath>
@@ -463,6 +463,32 @@ void edt(const at::Tensor& src, int64_t K, int64_t ignore_index, const c10::opti
                   optr<int32_t>(d2_in), optr<int32_t>(d2_out), cur_stream()),
         fn);
 }
+// Surface-distance metrics (surface.hip).  Softmax form: logits addressed by (sn, sk, sp) over N x K x H W with int64
+// labels [N, H, W]; binary form (K = 1): dense fp32 logits and target of N H W elements, the strides unused.  metrics
+// fp32 [N, K, 3], counts int64 [N, K, 2].  The workspace comes from the caching allocator per call.
+void surface_distances(const at::Tensor& logits, int64_t sn, int64_t sk, int64_t sp, int64_t N, int64_t K, int64_t H,
+                       int64_t W, const at::Tensor& target, int64_t ignore_index, double percentile,
+                       at::Tensor metrics, at::Tensor counts) {
+  const char* fn = "surface_distances";
+  const int64_t bytes = dlmpi_surface_ws_bytes(N, K, H, W);
+  if (bytes < 0) fail(fn, "served shapes: N >= 1, 1 <= H <= 4096, 1 <= W <= 16384, 1 <= K <= 256");
+  if (!(percentile > 0.0 && percentile <= 100.0)) fail(fn, "percentile must lie in (0, 100]");
+  const bool binary = target.scalar_type() != at::kLong;
+  if (binary) {
+    if (K != 1) fail(fn, "a float target is one class: K = 1");
+    dense(logits, at::kFloat, N * H * W, fn, "logits");
+    dense(target, at::kFloat, N * H * W, fn, "target");
+  } else {
+    pix_check(logits, sn, sk, sp, (int)N, (int)K, H * W, target, fn, "logits");
+  }
+  dense(metrics, at::kFloat, N * K * 3, fn, "metrics");
+  dense(counts, at::kLong, N * K * 2, fn, "counts");
+  at::Tensor ws = at::empty({bytes}, logits.options().dtype(at::kByte));   // the allocator's blocks are 512-B aligned
+  check(dlmpi_surface_distances(ptr<float>(logits), sn, sk, sp, target.data_ptr(), binary ? 1 : 0, N, (int)K, (int)H,
+                                (int)W, ignore_index, percentile / 100.0, ws.data_ptr(), ptr<float>(metrics),
+                                ptr<int64_t>(counts), cur_stream()),
+        fn);
+}
 // Boundary loss (boundary.hip).  boundary_weight: a finite float >= 0, or with bw_dev one fp32 on the device that the
 // kernels read; phi fp32 [N * K * HW] (softmax form) / [M] (sigmoid form).
 void boundary_weight_check(double plain, double bw, const c10::optional<at::Tensor>& bw_dev, const char* fn) {
@@ -577,6 +603,8 @@ void register_loss(pybind11::module& m) {
   m.def("edt_strip", []() { return dlmpi_edt_strip(); });
   m.def("edt_strip_rows", []() { return dlmpi_edt_strip_rows(); });
   m.def("edt", &edt);
+  m.def("surface_tile", []() { return dlmpi_surface_tile(); });
+  m.def("surface_distances", &surface_distances);
   m.def("boundary_softmax_fwd", &boundary_softmax_fwd);
   m.def("boundary_softmax_bwd", &boundary_softmax_bwd);
   m.def("boundary_sigmoid_fwd", &boundary_sigmoid_fwd);

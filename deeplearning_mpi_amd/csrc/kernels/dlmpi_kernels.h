@@ -538,6 +538,18 @@ hipError_t dlmpi_boundary_sigmoid_fwd(const float* logits, const float* target, 
 hipError_t dlmpi_boundary_sigmoid_bwd(const float* logits, const float* target, const float* phi, int64_t M,
                                       const float* go, float bce_weight, float bw_host, const float* bw_dev,
                                       float* dlogits, hipStream_t s);
+// Surface-distance metrics (surface.hip; the definition is at the top of that file): metrics fp32 [N][K][3] =
+// {Hausdorff, its percentile q * 100 (`linear` rule), ASSD}, counts int64 [N][K][2] = {|pred edge|, |gt edge|}; NaN
+// where both edge sets are empty, +inf where one is.  binary 0: logits addressed n sn + k sk + p sp, target int64
+// labels [N][H][W]; binary 1: K = 1, contiguous logits and fp32 target [N][H][W] (pred = x > 0, gt = t > 0.5).
+// Served (dlmpi_surface_ok): dlmpi_edt_ok of 2 N samples.  ws: dlmpi_surface_ws_bytes bytes (-1: a refused shape),
+// 16-byte aligned, nothing in it needs zeroing.  q in (0, 1].  No host read, no float atomics.
+int dlmpi_surface_tile();   // edge of the square tile of the edge pass
+int dlmpi_surface_ok(int64_t N, int64_t K, int64_t H, int64_t W);
+int64_t dlmpi_surface_ws_bytes(int64_t N, int64_t K, int64_t H, int64_t W);
+hipError_t dlmpi_surface_distances(const float* logits, int64_t sn, int64_t sk, int64_t sp, const void* target,
+                                   int binary, int64_t N, int K, int H, int W, int64_t ignore_index, double q,
+                                   void* ws, float* metrics, int64_t* counts, hipStream_t s);
 
 // eval
 hipError_t dlmpi_argmax_correct(const float* logits, int ldl, const int64_t* labels, int N, int K, int* correct,

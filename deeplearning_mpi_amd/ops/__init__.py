@@ -6,5 +6,5 @@ from .losses import (BCEBoundaryLoss, BCEDiceLoss, BCELovaszLoss, BCEWithLogitsL
                      bce_dice_loss, bce_lovasz_loss, bce_with_logits, boundary_loss, ce_boundary_loss, ce_dice_loss,
                      ce_lovasz_loss, cross_entropy, dice_loss, dice_multiclass, dice_per_sample, edt_squared,
                      lovasz_hinge, lovasz_softmax, mean_iou, ohem_bce_with_logits, ohem_cross_entropy, seg_counts,
-                     signed_distance_map, top1_correct)
+                     signed_distance_map, surface_distances, top1_correct)
 from ..data.mix import mix_batch_  # noqa: F401,E402  (the in-place mixup / CutMix kernel of data.hip)

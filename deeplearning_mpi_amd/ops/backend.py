@@ -692,6 +692,24 @@ class NativeBackend:
         self.C.edt(labels.contiguous(), K, int(ignore_index), phi, None, None)
         return phi if labels.dtype == torch.int64 else phi.view(N, H, W)
 
+    # Surface-distance metrics (surface.hip): edge pass, dlmpi_edt on the edge maps, scan, stable scatter, select.
+    # Workspace: 12 bytes per pixel and class + 24 per pixel, from the caching allocator per call.
+    @property
+    def surface_tile(self):
+        """Edge of the edge pass's square tile (the sizes around it are the edge cases of its tests)."""
+        return self.C.surface_tile()
+
+    def surface_distances(self, logits, target, ignore_index=-100, percentile=95.0):
+        """logits fp32 [N, K, H, W] (pixel_strides) with int64 labels, or contiguous [N, H, W] with an fp32 target
+        -> (metrics fp32 [N, K, 3] = {HD, HD percentile, ASSD}, counts int64 [N, K, 2] = {|P|, |G|})."""
+        binary = logits.dim() == 3
+        N, K, H, W = (logits.shape[0], 1, *logits.shape[1:]) if binary else logits.shape
+        metrics = torch.empty(N, K, 3, dtype=torch.float32, device=logits.device)
+        counts = torch.empty(N, K, 2, dtype=torch.int64, device=logits.device)
+        st = (0, 0, 1) if binary else pixel_strides(logits)
+        self.C.surface_distances(logits, *st, N, K, H, W, target, int(ignore_index), float(percentile), metrics, counts)
+        return metrics, counts
+
     @staticmethod
     def _boundary_weight(w):   # -> (the host float, the device scalar or None)
         return (0.0, w) if torch.is_tensor(w) else (float(w), None)
@@ -1463,6 +1481,57 @@ class RefBackend:
         root = d2.double().sqrt()
         phi = torch.where(d2 == self._EDT_INF, torch.zeros_like(root), torch.where(m, 1 - root, root)).to(self.dt)
         return phi if labels.dtype == torch.int64 else phi.view(N, H, W)
+
+    # Surface-distance metrics: the definition of csrc/kernels/surface.hip in plain torch (the CPU path)
+    surface_tile = 32   # the native edge pass's, so that tests take the same sizes on either backend
+
+    def surface_edges(self, logits, target, ignore_index=-100):
+        """-> int64 [2, N, H, W], the edge-label maps of pred and gt: the pixel's class where it is an edge pixel of
+        that map (a 4-neighbour, or the image border, is outside its class), else -1."""
+        if logits.dim() == 3:
+            maps = torch.stack([logits > 0, target > 0.5]).long() - 1
+        else:
+            K = logits.shape[1]
+            keep = self._pix_keep(target, K, ignore_index)
+            k = torch.arange(K, device=logits.device).view(1, K, 1, 1)
+            top = logits == logits.max(1, keepdim=True).values
+            pred = torch.where(top, k, torch.full_like(k, K)).min(1).values   # ties to the lowest index
+            none = torch.full_like(target, -1)
+            maps = torch.stack([torch.where(keep, pred, none), torch.where(keep, target, none)])
+        p = F.pad(maps, (1, 1, 1, 1), value=-1)
+        out = ((p[..., :-2, 1:-1] != maps) | (p[..., 2:, 1:-1] != maps) | (p[..., 1:-1, :-2] != maps)
+               | (p[..., 1:-1, 2:] != maps))
+        return torch.where((maps >= 0) & out, maps, torch.full_like(maps, -1))
+
+    def surface_distances(self, logits, target, ignore_index=-100, percentile=95.0):
+        binary = logits.dim() == 3
+        N, K, H, W = (logits.shape[0], 1, *logits.shape[1:]) if binary else logits.shape
+        edges = self.surface_edges(logits, target, ignore_index)
+        cls = torch.arange(K, device=logits.device).view(1, K, 1, 1)
+        metrics = torch.full((N, K, 3), float("nan"), dtype=torch.float64)
+        counts = torch.zeros(N, K, 2, dtype=torch.int64)
+        for n in range(N):
+            mask = edges[:, n].unsqueeze(1) == cls                                   # [2, K, H, W]
+            d2 = self.edt_squared(mask.reshape(2 * K, H, W)).view(2, K, H, W)
+            for c in range(K):
+                # direction 0: pred edge pixels to the gt edge set, 1: the reverse
+                lists = [d2[1 - m, c][mask[m, c]].sort().values.cpu() for m in (0, 1)]
+                counts[n, c] = torch.tensor([len(v) for v in lists])
+                if not all(len(v) for v in lists):
+                    if any(len(v) for v in lists):
+                        metrics[n, c] = float("inf")
+                    continue
+                quant = []
+                for v in lists:
+                    pos = (len(v) - 1) * (percentile / 100.0)
+                    lo = min(int(math.floor(pos)), len(v) - 1)
+                    hi = min(lo + 1, len(v) - 1)
+                    a, b = math.sqrt(int(v[lo])), math.sqrt(int(v[hi]))
+                    quant.append(a + (b - a) * (pos - lo))
+                total = sum(v.double().sqrt().sum().item() for v in lists)
+                metrics[n, c] = torch.tensor([math.sqrt(max(int(v[-1]) for v in lists)), max(quant),
+                                              total / sum(len(v) for v in lists)], dtype=torch.float64)
+        return metrics.to(torch.float32).to(logits.device), counts.to(logits.device)
 
     @staticmethod
     def _boundary_classes(K, include_background, like):

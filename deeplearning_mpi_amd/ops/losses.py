@@ -849,6 +849,36 @@ def seg_counts(logits, labels, ignore_index=-100) -> torch.Tensor:
 
 
 @torch.no_grad()
+def surface_distances(logits, target, ignore_index=-100, percentile=95.0):
+    """Surface-distance metrics per sample and class -> (``metrics`` fp32 [N, K, 3], ``counts`` int64 [N, K, 2]).
+    int64 ``target`` [N, H, W] with logits [N, K, H, W] (either pixel layout, read in place): pred = argmax (ties to
+    the lowest index), pixels whose label is ``ignore_index`` or outside [0, K) are in no class of either map.  A
+    float ``target`` with logits [N, H, W] or [N, 1, H, W]: pred = x > 0, gt = t > 0.5, the one class the foreground.
+    With P, G the 4-connected edge pixels of class c in pred and gt and D(A->B) the exact Euclidean distances of A's
+    pixels to the nearest pixel of B: ``metrics`` = {max(max D(P->G), max D(G->P)) (Hausdorff), the maximum over both
+    directions of the ``percentile``-th percentile by numpy's ``linear`` rule (HD95), (sum D(P->G) + sum D(G->P)) /
+    (|P| + |G|) (ASSD)}, ``counts`` = {|P|, |G|}.  NaN where both sets are empty, +inf where exactly one is.  On the
+    GPU csrc/kernels/surface.hip (H <= 4096, W <= 16384), no host synchronisation, the same bits on every run."""
+    if not 0.0 < float(percentile) <= 100.0:   # (a NaN fails too)
+        raise ValueError(f"surface_distances: percentile must lie in (0, 100], got {percentile}")
+    if target.dtype == torch.int64:
+        if logits.dim() != 4:
+            raise ValueError(f"surface_distances takes [N, K, H, W] logits with int64 labels, got "
+                             f"{tuple(logits.shape)}")
+        _check_pixel_args(logits, target)
+        be = _be(logits.device, logits.dtype)
+        return be.surface_distances(_pixel_layout(logits.detach()).to(be.dt), target.contiguous(), int(ignore_index),
+                                    float(percentile))
+    x = logits.squeeze(1) if logits.dim() == 4 and logits.shape[1] == 1 else logits
+    if x.dim() != 3 or not target.is_floating_point() or target.shape != x.shape:
+        raise ValueError(f"the binary surface_distances takes logits [N, H, W] or [N, 1, H, W] and a float target "
+                         f"[N, H, W], got {tuple(logits.shape)} and {target.dtype} {tuple(target.shape)}")
+    be = _be(logits.device, logits.dtype)
+    return be.surface_distances(x.detach().to(be.dt).contiguous(), target.to(be.dt).contiguous(), int(ignore_index),
+                                float(percentile))
+
+
+@torch.no_grad()
 def dice_multiclass(logits, labels, ignore_index=-100) -> torch.Tensor:
     """Per-sample Dice [N] of argmax(logits) against integer labels: the mean over the foreground
     classes 1..K-1 of (2 inter + 1e-8) / (pred + target + 1e-8); a class absent from both scores 1.0
